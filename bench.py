@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- the hot-path benchmark of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3w|c2|c2b|c3|c5|...] [--scaling strong|weak] [--rows R] [--no-cpu-baseline] [--no-also]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3w|c2|c2b|c3|c5|...] [--scaling strong|weak] [--rows R] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-also] [--no-predict]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Two ways to N GPUs, both through the product's door (the C operator rfx_select) and both planned by the library's one planner (rfx_exec.c):
@@ -31,6 +32,12 @@ Workloads (BASELINE.json configs / SURVEY 8d):
   k9   a10         select sum(v) by k, sparse keys (range > rows: open-addressing path)          16 B/row
   x6   8f-3        select sum(p*d) where q<24 and .05<=d<=.07   p, d: f64[1e9], q: i64[1e9]   24 B/row (TPC-H Q6 shape)
   c5   configs[4]  avg,min,max(d) where a<.316228 & b>.683772 & c!=.25   4 x f64[2e9]       32 B/row
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the roofline figure derived from that
+same timed loop.  `--full` adds everything that takes runs or checks of its own: the Engine leg verified against torch, the door's clocks,
+per-kernel and per-phase times, the reproducible modes, the secondary workloads (`also`), the boundary overhead, predicted_scaling and the
+CPU baselines; under a launcher / over N devices, the property check of the answer.
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float64; a fixed, seeded sample of rows when
+the whole would exceed 64 MB).
 One JSON line on stdout (rank 0); everything else goes to stderr.
 """
 from __future__ import annotations
@@ -311,6 +318,22 @@ class Job:
             return f"{n} ids: ascending, all selected, count equals torch's"
         return None
 
+    def outputs(self, res):
+        """The arrays a caller of step() receives from it, by name (--dump-outputs)."""
+        if self.name == "m2":
+            return {"mask": self._mask_keep}
+        if self.name == "g2":
+            return {"gathered": self._out_keep}
+        if self.name == "w2":
+            return {"ids": self._ids_keep}
+        if isinstance(res, dict):
+            out = {f"key{i}": k for i, k in enumerate(res["key_columns"])} if "key_columns" in res else {"keys": res["keys"]}
+            out["first"] = res["first"]
+            out.update({f"result{i}": r for i, r in enumerate(res["results"])})
+            return out
+        vals, sel = res
+        return {"values": [float("nan") if v is None else float(v) for v in vals], "selected": [sel]}
+
 
 def timed(job: Job, steps: int, warmup: int, world: int):
     eng = job.eng
@@ -344,8 +367,8 @@ def timed(job: Job, steps: int, warmup: int, world: int):
     return dt, sum(kms) / max(1, len(kms)), res
 
 
-def run_workload(name, eng, sharded, rows, row0, steps, warmup, world, total_rows=None):
-    """rows = this rank's rows; total_rows = rows of the whole job (all ranks)."""
+def run_workload(name, eng, sharded, rows, row0, steps, warmup, world, total_rows=None, full=True, dump=None):
+    """rows = this rank's rows; total_rows = rows of the whole job (all ranks).  full: verify the answer against torch; dump: --dump-outputs."""
     w = WORKLOADS[name]
     total_rows = rows * world if total_rows is None else total_rows
     import gc
@@ -358,7 +381,9 @@ def run_workload(name, eng, sharded, rows, row0, steps, warmup, world, total_row
     paths = dict(zip(PATHS, [eng.stat(i) - b for i, b in enumerate(before)]))
     planner = {k: eng.xstat(v) - xbefore[k] for k, v in XSTATS.items()}
     rtc = {k: v - rbefore[k] for k, v in rtc_counters(eng).items()}
-    checked = job.verify(res) if (world == 1 and sharded is None) else None
+    if dump:
+        dump_outputs(dump, job.outputs(res))
+    checked = job.verify(res) if (full and world == 1 and sharded is None) else None
     ms_step = dt * 1e3 / steps
     if name in ("c3", "c3w", "q2", "k9", "q1", "q7", "w2") or world > 1:
         kms = ms_step  # several dependent kernels (partition, aggregate, rank, emit) / the merge collective: price the whole query
@@ -410,6 +435,26 @@ def _brief(res):
         return {"groups": int(res["groups"])}
     vals, sel = res
     return {"values": vals, "selected": sel}
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most 64 MB: data as float64, plus a .npy header per array
+
+
+def dump_outputs(path, arrays):
+    """Every array (torch tensor, numpy array or list) as path/<name>.npy in float64.  When all of them together exceed DUMP_BYTES, every
+    array keeps the same share of its rows, drawn by a generator seeded with the array's length: equal inputs give equal samples."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    size = {k: int(v.numel()) if torch.is_tensor(v) else int(np.size(v)) for k, v in arrays.items()}
+    share = min(1.0, DUMP_BYTES / max(1, 8 * sum(size.values())))
+    for name, v in arrays.items():
+        n = size[name]
+        if share < 1.0 and n:
+            idx = np.unique(np.random.default_rng(n).integers(0, n, max(1, int(n * share))))
+            v = v[torch.from_numpy(idx).to(v.device)] if torch.is_tensor(v) else np.asarray(v)[idx]
+        a = v.double().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    log(f"[bench] --dump-outputs: {len(arrays)} array(s) in {path}" + (f", a seeded sample of {share:.2%} of the rows of each" if share < 1.0 else ""))
 
 
 def pmc_traffic(name):
@@ -649,11 +694,12 @@ def door_same(name, got, want, what):
             raise SystemExit(f"bench.py: rfx_select({name}) column {cname} differs from {what}")
 
 
-def c_door(name, eng, rows, steps, warmup, device_columns=False):
+def c_door(name, eng, rows, steps, warmup, device_columns=False, full=True, dump=None):
     """The workload through rfx_select -- the C operator boundary the reference's evaluator (or `loadfn`) binds -- at the workload's full size.
     Default: host vectors laid out as RayforceDB objects, pinned (uploaded once, trusted until rfx_invalidate); device_columns: the columns
-    stay where the device generator left them and the table's columns are device handles.  The answer of the last call is checked against
-    Engine's on the same data (itself checked against torch in run_workload)."""
+    stay where the device generator left them and the table's columns are device handles.  full: after the timed loop, the clocks, phases and
+    kernels of more calls, the reproducible modes, and the answer of the last call checked against Engine's on the same data (itself checked
+    against torch in run_workload); dump: --dump-outputs of that answer."""
     from rayforce_amd import hostobj as H
     ops = H.lib()
     ops.rfx_host_bind()
@@ -678,19 +724,26 @@ def c_door(name, eng, rows, steps, warmup, device_columns=False):
     d = H.select_dict(q, tab)
     dt, got = door_run(ops, H, d, steps, warmup)
     steps_ms = dict(door_run.last_steps_ms)
-    clocks = door_clocks(ops, H, d, eng.device.index) if "by" in q and not device_columns else None  # (right after the timed loop: the state `value` was measured in)
-    phases = door_phases(ops, H, d) if "by" in q else None
-    try:
-        kernels_ms = door_kernels(ops, H, d)
-    except Exception as e:  # noqa: BLE001
-        log(f"[bench] door_kernels failed: {e}")
-        kernels_ms = []
-    cols = keep if device_columns else door_columns(eng, spec, rows)
-    want = eng.select({"from": cols, **q})
-    door_same(name, got, want, "Engine.select on the same data")
-    del cols, want, keep
-    det = None
-    if "by" in q and not device_columns and os.environ.get("RFX_DETERMINISTIC") is None and os.environ.get("RFX_VALIDATE") is None:
+    if dump:
+        dump_outputs(dump, got)
+    result = {"groups": len(next(iter(got.values())))} if "by" in q else {"values": [float(v[0]) for v in got.values()]}
+    clocks, phases, kernels_ms, det = None, None, None, None
+    if not full:
+        steps_ms.pop("in_order")  # (a plain run's line stays short at any step count)
+    else:
+        clocks = door_clocks(ops, H, d, eng.device.index) if "by" in q and not device_columns else None  # (right after the timed loop: the state `value` was measured in)
+        phases = door_phases(ops, H, d) if "by" in q else None
+        try:
+            kernels_ms = door_kernels(ops, H, d)
+        except Exception as e:  # noqa: BLE001
+            log(f"[bench] door_kernels failed: {e}")
+            kernels_ms = []
+        cols = keep if device_columns else door_columns(eng, spec, rows)
+        want = eng.select({"from": cols, **q})
+        door_same(name, got, want, "Engine.select on the same data")
+        del cols, want
+    del keep
+    if full and "by" in q and not device_columns and os.environ.get("RFX_DETERMINISTIC") is None and os.environ.get("RFX_VALIDATE") is None:
         # the same query in the reproducible modes (grouped f64 sums as integer sums over the column's fixed-point image, one limb or two: DESIGN.md section 4):
         # the first call makes the image(s) (kept with the resident copy), the later ones run on them
         import numpy as np
@@ -739,7 +792,8 @@ def c_door(name, eng, rows, steps, warmup, device_columns=False):
             "rows": rows, "steps": steps, "ms_per_step": dt * 1e3 / steps, "rows_per_s": rows / (dt / steps), "answered_on_gpu": 1,
             "median_ms": steps_ms["median"], "rows_per_s_median": rows / (steps_ms["median"] * 1e-3),
             "steps_ms": steps_ms, "phases_ms": phases, "kernels_ms": kernels_ms,
-            "pin_upload_s": pin_s, "clocks": clocks, "deterministic_mode": det, "verified": "every result column equals Engine.select's on the same data (f64 within 1e-9)"}
+            "pin_upload_s": pin_s, "clocks": clocks, "deterministic_mode": det, "result": result,
+            "verified": "every result column equals Engine.select's on the same data (f64 within 1e-9)" if full else None}
 
 
 # ------------------------------------------------------------------------------------------------ the Amdahl budget of the sharded tail
@@ -899,8 +953,10 @@ def one_process(args):
     d = H.select_dict(q, tab)
     dt, got = door_run(ops, H, d, args.steps, args.warmup)
     steps_ms = dict(door_run.last_steps_ms)
-    phases = door_phases(ops, H, d) if "by" in q else None
-    checked = door_property_check(name, got, shards, q, lambda x: x)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, got)
+    phases = door_phases(ops, H, d) if args.full and "by" in q else None
+    checked = door_property_check(name, got, shards, q, lambda x: x) if args.full else None
     x = C.c_void_p(ops.rfx_ops_exec())
     w = WORKLOADS[name]
     ms = dt * 1e3 / args.steps
@@ -920,7 +976,7 @@ def one_process(args):
         if ranks_seen != len(uniq) or sorted(r for _, r in seen) != list(range(len(uniq))):
             raise SystemExit(f"bench.py: the communicators of the {len(uniq)} devices report (count, rank) = {seen}")
     cpu = None
-    if not args.no_cpu_baseline:  # the same bounded CPU sample as at N = 1 (the reference's CPU path does not change with the GPU count)
+    if args.full and not args.no_cpu_baseline:  # the same bounded CPU sample as at N = 1 (the reference's CPU path does not change with the GPU count)
         try:
             cpu = cpu_baseline(name, min(args.cpu_sample_rows, base, 20_000_000), timeout=45, pools=(32,), sweep_budget_s=20)  # (a smaller sample than N = 1's: N > 1 runs follow back to back)
         except Exception as e:  # noqa: BLE001
@@ -987,6 +1043,8 @@ def launcher_door(args, name, eng, world, rank, rows, row0, total_rows):
     tab = H.device_table(cols)
     d = H.select_dict(q, tab)
     dt, got = door_run(ops, H, d, args.steps, args.warmup, world)
+    if args.dump_outputs and rank == 0:  # (rank 0's answer: under rank slices, its range of the groups)
+        dump_outputs(args.dump_outputs, got)
 
     def reduce_sum(x):
         t = torch.tensor([x], dtype=torch.float64, device="cuda") if isinstance(x, float) else x.cuda()
@@ -994,7 +1052,7 @@ def launcher_door(args, name, eng, world, rank, rows, row0, total_rows):
             dist.all_reduce(t)
         return float(t[0]) if isinstance(x, float) else t.cpu()
 
-    checked = door_property_check(name, got, [cols], q, reduce_sum, sliced=sliced and world > 1)
+    checked = door_property_check(name, got, [cols], q, reduce_sum, sliced=sliced and world > 1) if args.full else None
     x = C.c_void_p(ops.rfx_ops_exec())
     w_, r_ = C.c_int(), C.c_int()
     if transport is None:
@@ -1144,11 +1202,14 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong: the workload's BASELINE row count in TOTAL, split over the ranks (SURVEY 8d C4/C5); weak: that many rows PER rank")
     ap.add_argument("--rows", type=int, default=0, help="override the workload's BASELINE row count (total under strong scaling, per rank under weak)")
+    ap.add_argument("--full", action="store_true", help="also the checks and the measurements that take runs of their own (see the module's doc); "
+                    "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path returned in its last step as DIR/<name>.npy (float64, <= 64 MB)")
     ap.add_argument("--cpu-sample-rows", type=int, default=100_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--sharded", action="store_true", help="use the row-sharded driver (collectives) even with one rank")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads in the 'also' field")
-    ap.add_argument("--no-predict", action="store_true", help="skip the predicted_scaling block (the query over rows / N on this device for N = 1, 2, 4, 8 + the stated merge model)")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary workloads in the 'also' field")
+    ap.add_argument("--no-predict", action="store_true", help="with --full: skip the predicted_scaling block (the query over rows / N on this device for N = 1, 2, 4, 8 + the stated merge model)")
     ap.add_argument("--engine-door", action="store_true", help="report Engine.group_by / filter_aggr (ctypes host, device-resident results) as `value` instead of rfx_select")
     ap.add_argument("--spawn", action="store_true", help="--gpus N without a launcher: start N ranks under torch.distributed.run (one process per GPU) instead of one process over N devices")
     ap.add_argument("--dry-run", action="store_true", help="no device work: rendezvous, shard arithmetic and the JSON line only (CPU test of the launch contract)")
@@ -1156,6 +1217,8 @@ def main():
     ap.add_argument("--ab", default="", help="dev: comma list of tune flags to A/B in ONE process (same box, same clocks); prints one line per run")
     ap.add_argument("--tune-flags", type=int, default=0, help="rfx_hip_ctx_tune flags (kernel-variant experiments)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if args.spawn or args.dry_run:
@@ -1239,7 +1302,7 @@ def main():
                 log(f"[ab] rep {rep} flags:bpc {item}: ms_per_step {dt * 1e3 / args.steps:.3f} kernel_ms {kms:.3f} "
                     f"GB/s {WORKLOADS[name]['bytes_per_row'] * rows / kms / 1e6:.0f}")
         return
-    ldoor = None
+    ldoor, main_r = None, None
     if (world > 1 or os.environ.get("RFX_BENCH_FORCE_LAUNCHER_DOOR")) and name in C_DOOR and name != "q7" and not args.engine_door:  # (the env: the N > 1 code on one rank)
         # every rank's shard through rfx_select, the operator layer's context inside the RCCL communicator: `value` is this door's
         if sharded is not None:
@@ -1253,17 +1316,20 @@ def main():
         main_r = dict(workload=name, rows_per_gpu=rows, total_rows=total_rows, ms_per_step=kms, rows_per_s=ldoor["rows_per_s"], kernel_ms=kms, achieved_GBps=ach,
                       frac=ach / HBM_PEAK_GBPS, result=ldoor["result"], verified=ldoor["verified"], paths={}, planner={}, rtc={})
         ranks_seen = ldoor["ranks_seen"]
-    else:
-        main_r = run_workload(name, eng, sharded, rows, row0, args.steps, args.warmup, world, total_rows)
-    log(f"[bench] {name}: {main_r}")
+    # the headline goes through the product's own door: the C operator rfx_select (with --full, Engine's time for the same query rides beside it)
+    use_door = world == 1 and sharded is None and ldoor is None and name in C_DOOR and not args.engine_door
+    if ldoor is None and (args.full or not use_door):
+        main_r = run_workload(name, eng, sharded, rows, row0, args.steps, args.warmup, world, total_rows, full=args.full,
+                              dump=None if use_door else args.dump_outputs)
+    if main_r:
+        log(f"[bench] {name}: {main_r}")
     door = None
-    if world == 1 and sharded is None and ldoor is None and name in C_DOOR and not args.engine_door:
-        # the headline goes through the product's own door: the C operator rfx_select (Engine's time for the same query rides beside it)
-        door = c_door(name, eng, rows, args.steps, args.warmup)
+    if use_door:
+        door = c_door(name, eng, rows, args.steps, args.warmup, full=args.full, dump=args.dump_outputs)
         log(f"[bench] {name} through rfx_select: {door}")
     also = {}
     FULL = ("c3w", "c2", "c2b", "c3", "c5")  # the BASELINE configs: the full step count, their own roofline block and CPU baseline
-    if not args.no_also and world == 1 and not args.rows:
+    if args.full and not args.no_also and world == 1 and not args.rows:
         for other in WORKLOADS:
             if other == name:
                 continue
@@ -1287,14 +1353,14 @@ def main():
                 also[other] = {"error": str(e)[:200]}
 
     boundary = None
-    if rank == 0 and world == 1 and not args.no_also and not args.rows:
+    if args.full and rank == 0 and world == 1 and not args.no_also and not args.rows:
         try:
             boundary = boundary_overhead(eng)
             log(f"[bench] boundary: {boundary}")
         except Exception as e:  # noqa: BLE001
             boundary = {"error": str(e)[:200]}
     predicted, predicted_more = None, {}
-    if rank == 0 and world == 1 and door and not args.rows and not args.no_predict:
+    if args.full and rank == 0 and world == 1 and door and not args.rows and not args.no_predict:
         try:
             predicted = predicted_scaling(name, eng)
             log(f"[bench] predicted_scaling: {predicted}")
@@ -1309,7 +1375,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 predicted_more[other] = {"error": str(e)[:200]}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(name, min(args.cpu_sample_rows, rows))
         except Exception as e:  # noqa: BLE001
@@ -1331,7 +1397,7 @@ def main():
 
     if rank == 0:
         w = WORKLOADS[name]
-        head = dict(main_r)
+        head = dict(main_r) if main_r else {"total_rows": total_rows, "rtc": rtc_counters(eng)}  # (a plain run times the door alone)
         if door:  # value = the C operator boundary; the Engine figures stay in `engine`
             # SURVEY 8d defines the metric on the MEDIAN step: `value`, `roofline.achieved / frac` come from it; `ms_per_step` stays the mean of the
             # timed loop (what a clock around the run sees) and the mean-based figures ride beside (value_mean, roofline.frac_mean)
@@ -1359,8 +1425,8 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"{name}: {w['desc']}", "rows_per_gpu": rows, "total_rows": total_rows,
                        "sharding": f"row-range x{world}" if world > 1 else "single GPU", "ranks_seen": ranks_seen, "resident": "HBM (columns generated on device)",
-                       "result": main_r["result"], "verified": main_r["verified"], "paths": main_r["paths"],
-                       "planner": main_r.get("planner"),
+                       "result": (main_r or door)["result"], "verified": (main_r or door)["verified"], "paths": main_r["paths"] if main_r else None,
+                       "planner": main_r.get("planner") if main_r else None,
                        "door": door["door"] if door else ("rfx_select on this rank's row range as device column handles, the operator layer's context in the RCCL "
                                                           "communicator (rfx_ops_dist_init): a grouped answer stays sliced over the ranks (rfx_ops_set_rank_slices)" if ldoor else
                                                           "Engine (ctypes host over the library's planner, results stay on the device)")},
@@ -1369,13 +1435,14 @@ def main():
             "value_basis": ("median step of the timed loop (SURVEY 8d); ms_per_step = its mean, value_mean = rows / mean step" if door else "mean step of the timed loop"),
             "value_mean": head.get("rows_per_s_mean", head["rows_per_s"]),
             "median_ms": door["median_ms"] if door else None,
-            "steps_ms_in_order": door["steps_ms"]["in_order"] if door else None,
+            "steps_ms_in_order": door["steps_ms"].get("in_order") if door else None,
             "rtc": {"launches_through_run_time_compiled_kernels": int(rl.value), "plans_compiled": int(rc.value),
                     "plans_loaded_from_the_disk_cache": int(rd.value), "code_objects_written": int(rw.value)},
         }
         if door:
             line["door"] = door
-            line["engine"] = {k: main_r[k] for k in ("ms_per_step", "rows_per_s", "frac")}
+            if main_r:
+                line["engine"] = {k: main_r[k] for k in ("ms_per_step", "rows_per_s", "frac")}
             line["roofline"]["frac_mean"] = head["frac_mean"]
             line["roofline"]["basis"] = "whole query through rfx_select (every kernel, the plan walk, the result's read-back and host table), median step; dominant_kernel = that kernel alone by HIP events"
             if door.get("kernels_ms"):  # the dominant kernel alone: HIP events on the stream it is launched on, averaged over 5 more (untimed) steps
@@ -1397,6 +1464,7 @@ def main():
         for other, pr in predicted_more.items():
             line["predicted_scaling_" + other] = pr
         print(json.dumps(line), flush=True)
+    if rank == 0 and args.full:
         # the same run in <= 2 KB, LAST on stderr: a truncated tail of the record still carries every workload and the engine / door split
         def r3(v):
             return None if v is None else round(float(v), 3)

@@ -230,3 +230,24 @@ def test_phase_handover_probe_runs_without_a_device(built):
         us = lib.rfx_exec_probe_handover_us(n, 500)
         assert 0.0 < us < 5000.0, (n, us)
     assert lib.rfx_exec_probe_handover_us(0, 10) < 0 and lib.rfx_exec_probe_handover_us(99, 10) < 0
+
+
+def test_bench_dump_outputs_float64_and_a_seeded_sample_past_the_budget(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; when they exceed the budget, every array of a length keeps the same
+    seeded rows, so that two runs (two builds) compare output for output, and the files stay within 64 MB."""
+    import torch
+    import bench
+    small = {"k": np.arange(5, dtype=np.int64), "s": np.linspace(0.0, 1.0, 5), "values": [1.5, float("nan")], "mask": torch.tensor([0, 1, 1], dtype=torch.int8)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    for name, v in small.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        want = v.double().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        assert got.dtype == np.float64 and np.array_equal(got, want, equal_nan=True), name
+    n = 6_000_000  # two columns of 48 MB each as float64
+    big = {"keys": np.arange(n, dtype=np.int64), "sums": np.arange(n, dtype=np.float64) * 0.5}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 64_000_000
+    keys, sums = np.load(tmp_path / "b" / "keys.npy"), np.load(tmp_path / "b" / "sums.npy")
+    assert keys.dtype == np.float64 and n // 4 < len(keys) < n and np.array_equal(sums, keys * 0.5)  # the same rows of both
+    assert np.array_equal(keys, np.load(tmp_path / "c" / "keys.npy"))  # and the same rows again

@@ -104,3 +104,31 @@ def test_c5_full_size_partition_of_unity(eng):
     assert abs(sel / n - 0.1) < 1e-3 and abs(av - s / c) <= RTOL * av and mn_all <= mn <= av <= mx <= mx_all
     del t
     torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("config", ["c3w", "c2"])
+def test_bench_plain_run_dumps_the_timed_answer(config, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: a plain run times exactly K steps, prints one short JSON line with the headline
+    fields, and writes the last timed step's answer as float64 .npy files, which equal the oracle's answer over the same seeded rows."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 2_000_000
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", str(n),
+                          "--workload", config, "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 8192, lines
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["door"]["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["unit"] == "rows/s" and rec["higher_is_better"] is True and rec["config"]["total_rows"] == n
+    assert "also" not in rec and rec["cpu_baseline"] is None  # (the secondary measurements are --full's)
+    want = rfo.select({"from": host_columns(config, n), **QUERIES[config]})
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{c}.npy" for c in want)
+    for c, w in want.items():
+        g = np.load(tmp_path / f"{c}.npy")
+        assert g.dtype == np.float64 and g.shape == w.shape, c
+        w = w.astype(np.float64)
+        assert np.all(np.abs(g - w) <= RTOL * np.maximum(np.abs(w), 1e-300)), c

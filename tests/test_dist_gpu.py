@@ -310,7 +310,7 @@ def test_bench_under_the_launcher_two_ranks_one_gpu(workload):
     import sys
     env = dict(os.environ, RFX_BENCH_SAME_DEVICE="1", RFX_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-                          str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "40000000", "--workload", workload],
+                          str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "40000000", "--workload", workload, "--full"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -335,7 +335,7 @@ def test_reproducible_sums_across_rank_counts():
     for ranks in (2, 1):
         env = dict(os.environ, RFX_DETERMINISTIC="1", HSA_ENABLE_IPC_MODE_LEGACY="0", RFX_BENCH_WHOLE_RESULT="1")  # (the digest is of the whole answer)
         env.update({"RFX_BENCH_SAME_DEVICE": "1", "RFX_BENCH_BACKEND": "gloo"} if ranks > 1 else {"RFX_BENCH_FORCE_LAUNCHER_DOOR": "1"})
-        cmd = [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--rows", "30000001", "--workload", "c3w", "--no-also", "--no-cpu-baseline", "--no-predict"]
+        cmd = [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--rows", "30000001", "--workload", "c3w", "--full", "--no-also", "--no-cpu-baseline", "--no-predict"]
         if ranks > 1:
             cmd = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + cmd
         out = subprocess.run([sys.executable] + cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
