@@ -177,6 +177,15 @@ int rfx_exec_groups_fetch_all(rfx_exec_t *x, const rfx_groups_t *g, int n, const
 int rfx_exec_groups_window(const rfx_groups_t *g, int64_t g0, int64_t n, rfx_groups_t *out);
 void rfx_exec_groups_free(rfx_exec_t *x, rfx_groups_t *g);
 
+/* ---- med (rfx_median.hip): one shard only (RFX_ELIMIT otherwise) ----
+ * rfx_exec_median: the scalar `med` of an i64 column over the query's selection (its preds, or its d_mask) -- ray_med's rule (core/math.c:2529-2626).
+ * rfx_exec_group_median: g->groups f64 cells into d_out (on shard 0) -- aggr_med's rule (core/aggr.c:2136-2247) over an i64 / timestamp (RFX_I64) or
+ * f64 column; `g` is rfx_exec_group_by's result for the same query (one key column, no xbar, one slice), every selected row counted in its key's group.
+ * Scratch beyond the kernels' (8 B per selected row + 24 B per group): dense keys a slot table of (key range) * 8 B, taken only when the range is at most
+ * rows + groups; sparse keys a group index column of 8 B per row.  RFX_ENOMEM when the device cannot hold it (nothing is left allocated). */
+int rfx_exec_median(rfx_exec_t *x, const rfx_query_t *q, const void *d_col, int32_t col_type, rfx_value_t *out);
+int rfx_exec_group_median(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_t *g, const void *d_col, int32_t col_type, void *d_out);
+
 /* ---- join index (index_left_join_obj, core/index.c:2886-2928): d_ids[i] = first right row whose key tuple equals left row i's, else null.
  * RFX_ESTATE with *collision = 1: two key tuples share one 64-bit row hash (nothing may be used).  One shard. */
 int rfx_exec_join_index(rfx_exec_t *x, const void *const *d_left_keys, const void *const *d_right_keys, int nkeys, int64_t nleft, int64_t nright,

@@ -612,6 +612,38 @@ int rfx_hip_unfix_f64(rfx_ctx_t *ctx, int64_t *d_hi_io, const int64_t *d_lo, con
  * (`by: {t: (xbar ts 60000)}`). */
 int rfx_hip_xbar_i64(rfx_ctx_t *ctx, const int64_t *d_col, int64_t nrows, int64_t width, int64_t *d_out);
 
+/* ---- exact medians (rfx_median.hip): `med` scalar (ray_med, core/math.c:2529-2626) and grouped (aggr_med, core/aggr.c:2136-2247) ----
+ * A group's median is its selected values of ranks (l-1)/2 and l/2 -- nulls included -- under the reference's sort keys (core/sort.c:266-311:
+ * i64 x ^ 2^63; f64 NaN -> 0, negative -> ~bits, else bits | 2^63), combined by the reference's formula:
+ *   odd l: (f64)x[l/2].   Even l: RFX_MED_GROUPED  i64 ((f64)x[l/2-1] + (f64)x[l/2]) / 2.0, f64 (x[l/2-1] + x[l/2]) / 2.0;
+ *                                 RFX_MED_SCALAR   (f64)(x[l/2-1] + x[l/2], added as i64 and wrapping) / 2.0 (i64 only).
+ * An empty group answers NaN (null).  Which rows count, and in which group (all in one kernel pass: nothing per row is materialised):
+ *   preds / npred / logic   the where: as rfx_pred_t (every form the fused passes take), and/or
+ *   d_mask                  a B8 selection (nonzero = selected), may be NULL;
+ *   d_gids                  per row the group index in [0, groups) -- anything else is not counted -- or
+ *   d_key + d_table         the group of row r is d_table[d_key[r] - kmin] (range cells; out of range / outside [0, groups): not counted), or
+ *   neither                 (groups == 1) every selected row.
+ * Scratch: 8 B per selected row + 24 B per group (+ 4 KB per segment above 8192 rows), all rfx_hip_malloc'ed and freed before return (syncs). */
+enum { RFX_MED_GROUPED = 0, RFX_MED_SCALAR = 1 };
+typedef struct rfx_med_rows {
+    const rfx_pred_t *preds;
+    int32_t npred, logic;
+    const int8_t *d_mask;
+    const int64_t *d_gids;
+    const int64_t *d_key;
+    const int64_t *d_table;
+    int64_t kmin, range;
+} rfx_med_rows_t;
+/* d_out[g] (f64, groups cells) = the median of group g's selected values of d_val (RFX_I64 or RFX_F64; TIMESTAMP is RFX_I64) */
+int rfx_hip_group_median(rfx_ctx_t *ctx, const rfx_med_rows_t *rows, const void *d_val, int32_t val_type, int64_t nrows, int64_t groups, int32_t rule,
+                         double *d_out);
+/* the scalar `med` of an i64 column over the selected rows (RFX_MED_SCALAR), *out an f64 value (null when nothing is selected) */
+int rfx_hip_median(rfx_ctx_t *ctx, const rfx_pred_t *preds, int npred, int logic, const int8_t *d_mask, const int64_t *d_val, int64_t nrows, rfx_value_t *out);
+/* d_table[key - kmin] = g for every group key d_keys[g] inside the range, null elsewhere (range cells): the slot -> group table of a dense result */
+int rfx_hip_key_slot_table(rfx_ctx_t *ctx, const int64_t *d_keys, int64_t groups, int64_t kmin, int64_t range, int64_t *d_table);
+/* d_out[i] = the sort key of value i (the order the medians rank by) */
+int rfx_hip_median_keys(rfx_ctx_t *ctx, const void *d_val, int32_t val_type, int64_t n, uint64_t *d_out);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -117,6 +117,9 @@ rfx_obj_p rfx_min(rfx_obj_p x);
 rfx_obj_p rfx_max(rfx_obj_p x);
 rfx_obj_p rfx_count(rfx_obj_p x);
 rfx_obj_p rfx_first(rfx_obj_p x);
+/* ray_med (core/math.c:2529-2626): an I64 vector, a MAPFILTER over one, or a MAPGROUP (IDS / SHIFT index, with or without filter ids) over I64 /
+ * TIMESTAMP / F64 values -> the exact median(s) as F64 (rfx_median.hip); every other argument is the host's ray_med */
+rfx_obj_p rfx_med(rfx_obj_p x);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

@@ -82,6 +82,15 @@ class _ValUnion(C.Union):
     _fields_ = [("i", C.c_int64), ("f", C.c_double)]
 
 
+RFX_MED_GROUPED, RFX_MED_SCALAR = 0, 1
+
+
+class MedRows(C.Structure):
+    """rfx_med_rows_t: which rows a median counts, and in which group"""
+    _fields_ = [("preds", C.c_void_p), ("npred", C.c_int32), ("logic", C.c_int32), ("d_mask", C.c_void_p), ("d_gids", C.c_void_p),
+                ("d_key", C.c_void_p), ("d_table", C.c_void_p), ("kmin", C.c_int64), ("range", C.c_int64)]
+
+
 class Value(C.Structure):
     _anonymous_ = ("u",)
     _fields_ = [("type", C.c_int32), ("is_null", C.c_int32), ("u", _ValUnion)]
@@ -257,6 +266,10 @@ PROTOTYPES = {
     "rfx_hip_hash_mix_u64": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]),
     "rfx_agg_input_type": (C.c_int, [_P(Agg)]),
     "rfx_hip_xbar_i64": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_group_median": (C.c_int, [_ctx, _P(MedRows), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "rfx_hip_median": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(Value)]),
+    "rfx_hip_median_keys": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "rfx_hip_key_slot_table": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "rfx_hip_eval_expr": (C.c_int, [_ctx, _P(Agg), C.c_int64, C.c_void_p, _P(C.c_int32)]),
     "rfx_hip_join_probe_dense": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "rfx_hip_join_probe_hash": (C.c_int, [_ctx, C.c_void_p, C.c_int64, _P(HashTables), C.c_void_p]),
@@ -313,6 +326,8 @@ EXEC_PROTOTYPES = {
     "rfx_exec_groups_free": (None, [_exec, _P(Groups)]),
     "rfx_exec_timing": (None, [_exec, C.c_int]),
     "rfx_exec_probe_handover_us": (C.c_double, [C.c_int, C.c_int]),
+    "rfx_exec_median": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_int32, _P(Value)]),
+    "rfx_exec_group_median": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rfx_exec_join_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_join_index_shard": (C.c_int, [_exec, C.c_int, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_stat": (C.c_int64, [_exec, C.c_int]),

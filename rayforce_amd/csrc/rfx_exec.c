@@ -84,3 +84,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_merge.c"
 #include "rfx_exec_groupby.c"
 #include "rfx_exec_result.c"
+#include "rfx_exec_median.c"

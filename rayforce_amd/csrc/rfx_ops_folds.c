@@ -434,3 +434,108 @@ rfx_obj_p rfx_min(rfx_obj_p x) { return fold_op(F_MIN, RFX_AGG_MIN, x); }
 rfx_obj_p rfx_max(rfx_obj_p x) { return fold_op(F_MAX, RFX_AGG_MAX, x); }
 rfx_obj_p rfx_count(rfx_obj_p x) { return fold_op(F_COUNT, RFX_AGG_COUNT, x); }
 rfx_obj_p rfx_first(rfx_obj_p x) { return fold_op(F_FIRST, RFX_AGG_FIRST, x); }
+
+/* ---- (med x): ray_med (core/math.c:2529-2626) -- an I64 vector or a MAPFILTER over one (filter_collect, then the scalar rule), a MAPGROUP over I64 /
+ * TIMESTAMP / F64 values (aggr_med: the grouped rule) -- exact medians on the device (rfx_median.hip).  (ray_med itself reaches neither lazy arm: its
+ * l = ray_cnt(x)->i64 reads such a pair's count as 0 and answers null; a host that registers this function as its own `med` aggregate gets the
+ * medians those arms compute.  rfx_select follows ray_select and leaves med under by: / where: to the host.)  The MAPGROUP's rows are counted in their group
+ * straight from the index: IDS through its id column, SHIFT through its key table and source column (gathered by the filter ids, as fold_mapgroup does).
+ * Everything else -- other types, parted / window indexes, sharded columns -- is the host's own ray_med. */
+static obj_p med_host(obj_p x, const char *why) {
+    if (H.bound == 1 && H.f[F_MED]) return HOST_CALL(((rfx_unary_f)H.f[F_MED])(x));
+    char b[256];
+    snprintf(b, sizeof(b), "med: not covered by the MI355X path (%s) and no host ray_med to delegate to", why);
+    return fail(b);
+}
+static obj_p med_impl(obj_p x) {
+    rfx_host_bind();
+    if (!x) return fail("med: null argument");
+    const int mg = x->type == RFX_TYPE_MAPGROUP, mf = x->type == RFX_TYPE_MAPFILTER;
+    obj_p val = (mg || mf) ? RFX_AS_LIST(x)[0] : x;
+    if (!(val->type == RFX_TYPE_I64 || (mg && (val->type == RFX_TYPE_TIMESTAMP || val->type == RFX_TYPE_F64)))) return med_host(x, "value type");
+    if (mf && RFX_AS_LIST(x)[1]->type != RFX_TYPE_I64) return med_host(x, "filter ids");
+    if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
+    if (g_nshards > 1) return med_host(x, "sharded columns");
+    void *tmp[4] = {0};
+    int ntmp = 0;
+    obj_p res = NULL;
+    const void *dv = NULL;
+    if (resident(val, 0, &dv) != RFX_OK) return fail_hip("column upload");
+    if (!mg) { /* the scalar rule over the vector, or over the values at the filter's ids */
+        int64_t n = val->len;
+        if (mf) {
+            obj_p ids = RFX_AS_LIST(x)[1];
+            const void *di;
+            n = ids->len;
+            if (transient(ids, &di) != RFX_OK || rfx_hip_malloc(g_ctx, &tmp[ntmp], (size_t)(n ? n : 1) * 8) != RFX_OK) return fail_hip("filter upload");
+            ntmp++;
+            if (rfx_hip_gather_checked(g_ctx, dv, val->len, RFX_I64, (const int64_t *)di, n, tmp[0]) != RFX_OK) { res = fail_hip("gather"); goto done; }
+            dv = tmp[0];
+        }
+        rfx_value_t v;
+        if (rfx_hip_median(g_ctx, NULL, 0, RFX_AND, NULL, (const int64_t *)dv, n, &v) != RFX_OK) { res = fail_hip("med"); goto done; }
+        res = H.f64(v.f);
+        goto done;
+    }
+    {
+        obj_p index = RFX_AS_LIST(x)[1];
+        if (!index || index->type != RFX_TYPE_LIST || index->len != 7) return fail("med: malformed group index");
+        obj_p *ix = RFX_AS_LIST(index);
+        const int64_t itype = ix[0]->i64, groups = ix[1]->i64;
+        obj_p gids = ix[2], source = ix[4], filter = ix[5];
+        if (itype != RFX_INDEX_TYPE_IDS && itype != RFX_INDEX_TYPE_SHIFT) return med_host(x, "parted / window index");
+        if (!gids || gids->type != RFX_TYPE_I64 || groups < 0) return med_host(x, "group ids");
+        if (itype == RFX_INDEX_TYPE_SHIFT && !(source && source->type > 0 && col_ctype(source) == RFX_I64)) return med_host(x, "source column");
+        const int filtered = filter && filter->type == RFX_TYPE_I64;
+        const int64_t n = filtered ? filter->len : (itype == RFX_INDEX_TYPE_IDS ? gids->len : source->len);
+        if (itype == RFX_INDEX_TYPE_IDS && gids->len != n) return fail("med: group ids / filter length mismatch");
+        if (!filtered && val->len != n) return fail("length");
+        if (groups == 0) return H.vector(RFX_TYPE_F64, 0);
+        if (itype == RFX_INDEX_TYPE_SHIFT && gids->len <= 0) return med_host(x, "empty key table"); /* (before any device scratch is taken) */
+        rfx_med_rows_t rows;
+        memset(&rows, 0, sizeof(rows));
+        rows.logic = RFX_AND;
+        const void *dfl = NULL, *dk = NULL, *dt = NULL;
+        if (filtered) {
+            if (transient(filter, &dfl) != RFX_OK || rfx_hip_malloc(g_ctx, &tmp[ntmp], (size_t)(n ? n : 1) * 8) != RFX_OK) { res = fail_hip("filter upload"); goto done; }
+            ntmp++;
+            if (rfx_hip_gather_checked(g_ctx, dv, val->len, col_ctype(val), (const int64_t *)dfl, n, tmp[0]) != RFX_OK) { res = fail_hip("gather"); goto done; }
+            dv = tmp[0];
+        }
+        if (itype == RFX_INDEX_TYPE_IDS) {
+            if (transient(gids, &dk) != RFX_OK) { res = fail_hip("group ids upload"); goto done; }
+            rows.d_gids = (const int64_t *)dk;
+        } else {
+            if (resident(source, 0, &dk) != RFX_OK || transient(gids, &dt) != RFX_OK) { res = fail_hip("column upload"); goto done; }
+            if (filtered) {
+                if (rfx_hip_malloc(g_ctx, &tmp[ntmp], (size_t)(n ? n : 1) * 8) != RFX_OK) { res = fail_hip("scratch"); goto done; }
+                if (rfx_hip_gather_checked(g_ctx, dk, source->len, RFX_I64, (const int64_t *)dfl, n, tmp[ntmp]) != RFX_OK) { ntmp++; res = fail_hip("gather"); goto done; }
+                dk = tmp[ntmp++];
+            }
+            rows.d_key = (const int64_t *)dk;
+            rows.d_table = (const int64_t *)dt;
+            rows.kmin = ix[3]->i64;
+            rows.range = gids->len;
+        }
+        void *dout = NULL;
+        if (rfx_hip_malloc(g_ctx, &dout, (size_t)groups * 8) != RFX_OK) { res = fail_hip("result"); goto done; }
+        tmp[ntmp++] = dout;
+        obj_p out = H.vector(RFX_TYPE_F64, groups);
+        if (rfx_hip_group_median(g_ctx, &rows, dv, col_ctype(val), n, groups, RFX_MED_GROUPED, (double *)dout) != RFX_OK ||
+            rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), dout, (size_t)groups * 8) != RFX_OK) {
+            H.drop(out);
+            res = fail_hip("med over a MAPGROUP");
+            goto done;
+        }
+        res = out;
+    }
+done:
+    for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
+    return res;
+}
+rfx_obj_p rfx_med(rfx_obj_p x) {
+    op_begin();
+    obj_p r = med_impl(x);
+    op_end();
+    return r;
+}

@@ -39,6 +39,10 @@ typedef struct {
     signed char det_lo[RFX_MAX_AGGS];
     int det_k[RFX_MAX_AGGS], det_m[RFX_MAX_AGGS];
     int nhidden, det_cnt;
+    /* (med column): aggregate a is a COUNT stand-in that keeps the column's place in the planner's pass; its cell is rfx_exec_median's
+     * answer instead (F64) */
+    unsigned char med[RFX_MAX_AGGS];
+    int nmed;
 } sel_maps_t;
 /* result cells of an aggregate over a widened 4-byte column, back in the column's own width: the i64 null and the i64 identities of an
  * all-null group (core/aggr.c:1246) become the 4-byte ones */
@@ -58,6 +62,8 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
     memset(M->det_lo, -1, sizeof(M->det_lo));
     memset(M->det_on, 0, sizeof(M->det_on));
     memset(M->det_avg, 0, sizeof(M->det_avg));
+    memset(M->med, 0, sizeof(M->med));
+    M->nmed = 0;
     for (int64_t i = 0; i < dkeys->len; i++) {
         int64_t k = RFX_AS_I64(dkeys)[i];
         if (k == s_from || k == s_where || k == s_by || k == s_take) continue;
@@ -67,6 +73,30 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
         int f = fn_id(RFX_AS_LIST(e)[0]);
         obj_p a = RFX_AS_LIST(e)[1];
         static const int KIND[] = {RFX_AGG_SUM, RFX_AGG_AVG, RFX_AGG_MIN, RFX_AGG_MAX, RFX_AGG_COUNT, RFX_AGG_FIRST};
+        if (f == F_MED) {
+            /* (med column): scalar over an I64 column, no where: -- ray_med of the column itself (ray_med has no F64 / TIMESTAMP arm: its err_type is the
+             * host's to raise).  Under by: and under where: ray_select hands ray_med a lazy MAPGROUP / MAPFILTER pair, and ray_med's first step,
+             * l = ray_cnt(x)->i64 (core/math.c:2530), reads the count of such a pair as 0 (ray_cnt has no arm for it): the reference answers null
+             * there, never a median.  Those shapes stay the host's, so that this entry point never answers differently. */
+            if (a->type != -RFX_TYPE_SYMBOL) { *why = "med of an expression"; return SEL_OUT; }
+            if (grouped) { *why = "med under by: (ray_med of a MAPGROUP pair answers null in the reference)"; return SEL_OUT; }
+            obj_p c = table_col(tab, a->i64);
+            if (!c || (g_npx && proxy_of(c)) || c->type != RFX_TYPE_I64) {
+                *why = "med: column type";
+                return SEL_OUT;
+            }
+            const void *d;
+            if (resident(c, 0, &d) != RFX_OK) return SEL_DONE;
+            memset(&M->aggs[n], 0, sizeof(M->aggs[n]));
+            M->aggs[n].kind = RFX_AGG_COUNT;
+            M->aggs[n].d_col = d;
+            M->aggs[n].col_type = col_ctype(c);
+            M->outtype[n] = RFX_TYPE_F64;
+            M->med[n] = 1;
+            M->nmed++;
+            M->names[M->nagg++] = k;
+            continue;
+        }
         if (f < F_SUM || f > F_FIRST) { *why = "mapping is not (aggr ...)"; return SEL_OUT; }
         memset(&M->aggs[n], 0, sizeof(M->aggs[n]));
         M->aggs[n].kind = KIND[f - F_SUM];
@@ -577,6 +607,12 @@ static obj_p select_impl(obj_p dict) {
             if (mrc == SEL_DONE) { res = fail_hip("column upload"); goto done; }
             if (mrc == SEL_OUT) goto out;
         }
+        if (M.nmed) { /* med: no where: (see sel_mappings), one shard of an in-memory table, one process */
+            if (where) { why = "med under where: (ray_med of a MAPFILTER pair answers null in the reference)"; goto out; }
+            if (parted) { why = "med over a parted table"; goto out; }
+            if (g_nshards > 1) { why = "med over a sharded table"; goto out; }
+            if (rfx_exec_ranks(g_x, NULL) > 1) { why = "med over several ranks"; goto out; }
+        }
         /* by: a column symbol, or a dict {name: column ...} (get_gkeys / get_gvals, core/query.c:165-240) */
         obj_p kcs[RFX_MAX_KEYS] = {0};
         const void *dks[RFX_MAX_KEYS] = {0};
@@ -710,6 +746,12 @@ static obj_p select_impl(obj_p dict) {
         rfx_value_t vals[RFX_MAX_AGGS];
         int64_t selected = 0;
         if (rfx_exec_filter_aggr(g_x, &Q, vals, &selected) != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
+        for (int a = 0; a < M.nagg; a++) {
+            if (!M.med[a]) continue;
+            const int mrc = rfx_exec_median(g_x, &Q, M.aggs[a].d_col, M.aggs[a].col_type, &vals[a]);
+            if (mrc == RFX_ENOMEM) { why = "med: device scratch (8 B per row) not available"; goto out; }
+            if (mrc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
+        }
         res = sel_build_scalar(vals, &M);
         g_last_gpu = 1;
         goto done;
