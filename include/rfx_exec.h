@@ -186,6 +186,16 @@ void rfx_exec_groups_free(rfx_exec_t *x, rfx_groups_t *g);
 int rfx_exec_median(rfx_exec_t *x, const rfx_query_t *q, const void *d_col, int32_t col_type, rfx_value_t *out);
 int rfx_exec_group_median(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_t *g, const void *d_col, int32_t col_type, void *d_out);
 
+/* ---- sort (rfx_sort.hip): one shard only (RFX_ELIMIT "sort over a sharded table": a sharded merge sort is its own piece of work) ----
+ * rfx_exec_sort: d_perm (n i64 cells on shard 0) = the stable lexicographic order of the rows by d_cols[0] (most significant) .. d_cols[ncols-1],
+ * all ascending or all descending -- one stable radix sort per column from the last to the first, each reading its keys through the running
+ * permutation (core/order.c:266-321,354-409); ties keep ascending row order in both directions.  types[k]: RFX_I64 (also TIMESTAMP) or RFX_F64.
+ * rfx_exec_sort_values: d_out = the column's own cells in that order (asc / desc), d_perm (may be NULL) the permutation as well.
+ * Rows <= 2^32 - 1; scratch 24 B per row (+ one more permutation of 8 B per row when ncols > 1), freed before return; RFX_ENOMEM when it does not fit.
+ * RFX_XSTAT_SORTS / RFX_XSTAT_SORT_PASSES count what ran. */
+int rfx_exec_sort(rfx_exec_t *x, const void *const *d_cols, const int32_t *types, int ncols, int descending, int64_t n, int64_t *d_perm);
+int rfx_exec_sort_values(rfx_exec_t *x, const void *d_col, int32_t type, int descending, int64_t n, void *d_out, int64_t *d_perm);
+
 /* ---- join index (index_left_join_obj, core/index.c:2886-2928): d_ids[i] = first right row whose key tuple equals left row i's, else null.
  * RFX_ESTATE with *collision = 1: two key tuples share one 64-bit row hash (nothing may be used).  One shard. */
 int rfx_exec_join_index(rfx_exec_t *x, const void *const *d_left_keys, const void *const *d_right_keys, int nkeys, int64_t nleft, int64_t nright,
@@ -219,7 +229,9 @@ enum {
     RFX_XSTAT_NS_EMIT = 13,
     RFX_XSTAT_NS_FETCH = 14,
     RFX_XSTAT_NS_TOTAL = 15,     /* rfx_exec_group_by entry to exit, + the fetches */
-    RFX_XSTAT_N = 16
+    RFX_XSTAT_SORTS = 16,        /* sorts (one per key column of a multi-column sort) answered by the device path */
+    RFX_XSTAT_SORT_PASSES = 17,  /* ... radix passes they executed (a digit every key agrees on costs none) */
+    RFX_XSTAT_N = 18
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

@@ -644,6 +644,22 @@ int rfx_hip_key_slot_table(rfx_ctx_t *ctx, const int64_t *d_keys, int64_t groups
 /* d_out[i] = the sort key of value i (the order the medians rank by) */
 int rfx_hip_median_keys(rfx_ctx_t *ctx, const void *d_val, int32_t val_type, int64_t n, uint64_t *d_out);
 
+/* ---- stable radix sort (rfx_sort.hip): the order behind iasc / idesc / asc / desc / rank / xasc / xdesc (core/sort.c, core/order.c) ----
+ * Rows are ordered by the medians' sort key u(x) above (descending: by ~u(x)); equal keys keep their ascending row order in BOTH directions.
+ * So nulls (NULL_I64, any NaN) come first ascending and last descending, -0.0 < +0.0.  type: RFX_I64 (also TIMESTAMP) or RFX_F64.
+ * An LSD radix sort over 8-bit digits of (u64 key, u32 row) records; a digit on which every key agrees costs no pass (*passes, may be NULL,
+ * receives the number that ran: 0..8).  n <= 2^32 - 1 rows (RFX_ELIMIT above).  Scratch: 24 B per row + 1 KB per tile of 16384 rows (2048
+ * below 2^23 rows), rfx_hip_malloc'ed and freed before return (syncs); RFX_ENOMEM when the device cannot hold it.
+ * rfx_hip_sort_index: d_perm_out[j] = the row at place j.  With d_perm_in (one level of a multi-column sort) the keys are read through it --
+ *   u(d_col[d_perm_in[i]]) -- and d_perm_out[j] = d_perm_in[src(j)]; d_perm_in == NULL is 0..n-1.  d_perm_out may not alias d_perm_in.
+ * rfx_hip_sort_values: d_out[j] = the ORIGINAL cell at place j (decoded from the key; a NaN takes its own sign and payload from the column
+ *   through its row); d_perm_out (may be NULL) receives the permutation as well.
+ * rfx_hip_inverse_perm: d_out[d_perm[i]] = i (`rank`); entries outside [0, n) are ignored. */
+int rfx_hip_sort_index(rfx_ctx_t *ctx, const void *d_col, int32_t type, int64_t n, int descending, const int64_t *d_perm_in, int64_t *d_perm_out,
+                       int32_t *passes);
+int rfx_hip_sort_values(rfx_ctx_t *ctx, const void *d_col, int32_t type, int64_t n, int descending, void *d_out, int64_t *d_perm_out, int32_t *passes);
+int rfx_hip_inverse_perm(rfx_ctx_t *ctx, const int64_t *d_perm, int64_t n, int64_t *d_out);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

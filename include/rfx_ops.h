@@ -31,6 +31,10 @@
  *   rfx_add rfx_sub        ray_add ray_sub       core/math.c:2280-2345 (binop_map)   binary_f  vector (x) vector | atom -> vector
  *   rfx_mul rfx_div        ray_mul ray_fdiv (`div`)                                  binary_f  (i64 / f64, the reference's promotion)
  *   rfx_floordiv rfx_mod   ray_div (`/`: floor division, left operand's type) ray_mod (`%`)   binary_f  (core/math.c:1138-1364, 1449-1530)
+ *   rfx_iasc rfx_idesc     ray_iasc ray_idesc    core/order.c:32-72              unary_f   I64 / TIMESTAMP / F64 vector -> I64 permutation
+ *   rfx_asc rfx_desc       ray_asc ray_desc      core/order.c:74-244             unary_f   -> the sorted cells, ATTR_ASC / ATTR_DESC
+ *   rfx_rank               ray_rank              core/order.c:519-556            unary_f   -> the inverse of iasc
+ *   rfx_xasc rfx_xdesc     ray_xasc ray_xdesc    core/order.c:246-420            binary_f  (table, column symbol | symbol vector) -> table
  *
  * Everything below runs on the MI355X through the flat ABI of rfx_hip.h.  There is NO CPU implementation behind these
  * entry points: queries whose shape the GPU path does not cover are handed back to the host's own ray_* function when
@@ -120,6 +124,20 @@ rfx_obj_p rfx_first(rfx_obj_p x);
 /* ray_med (core/math.c:2529-2626): an I64 vector, a MAPFILTER over one, or a MAPGROUP (IDS / SHIFT index, with or without filter ids) over I64 /
  * TIMESTAMP / F64 values -> the exact median(s) as F64 (rfx_median.hip); every other argument is the host's ray_med */
 rfx_obj_p rfx_med(rfx_obj_p x);
+/* ray_iasc / ray_idesc / ray_asc / ray_desc / ray_rank (core/order.c:32-244,519-556) of an I64 / TIMESTAMP / F64 vector, ray_xasc / ray_xdesc
+ * (core/order.c:246-420) of a table of 8-byte columns by one symbol or a symbol vector of I64 / TIMESTAMP / F64 columns: a stable radix sort on the
+ * device (rfx_sort.hip).  Nulls first ascending, last descending; ties in ascending row order in both directions; asc / desc return the original
+ * cells with ATTR_ASC / ATTR_DESC (| the argument's ATTR_DISTINCT); an argument carrying ATTR_ASC / ATTR_DESC is answered from the attribute as the
+ * reference does.  Every other shape (SYMBOL / LIST / DICT / ENUM / 1-2-4-byte keys, other column types, sharded columns) is the host's own verb. */
+rfx_obj_p rfx_iasc(rfx_obj_p x);
+rfx_obj_p rfx_idesc(rfx_obj_p x);
+rfx_obj_p rfx_asc(rfx_obj_p x);
+rfx_obj_p rfx_desc(rfx_obj_p x);
+rfx_obj_p rfx_rank(rfx_obj_p x);
+rfx_obj_p rfx_xasc(rfx_obj_p t, rfx_obj_p cols);
+rfx_obj_p rfx_xdesc(rfx_obj_p t, rfx_obj_p cols);
+/* 1: the last of those seven calls ran the device sort; 0: it was answered from an attribute / an empty argument, or handed to the host */
+int rfx_last_sort_on_gpu(void);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

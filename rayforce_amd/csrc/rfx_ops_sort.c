@@ -1,0 +1,203 @@
+/* rfx_ops_sort.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own).
+ * iasc / idesc / asc / desc / rank / xasc / xdesc (core/order.c:32-556, core/sort.c:430-479,691-740) over I64 / TIMESTAMP / F64 keys on the device
+ * (rfx_sort.hip through rfx_exec_sort); every other shape -- SYMBOL keys (the reference compares strings), LIST / DICT / ENUM, 1/2/4-byte keys,
+ * tables holding a column that is not an 8-byte vector, columns spread over shards -- is the host's own verb, the reason in rfx_ops_last_error(). */
+#define ATTR_DISTINCT_ 1
+#define ATTR_ASC_ 2
+#define ATTR_DESC_ 4
+enum { SORT_IASC, SORT_IDESC, SORT_ASC, SORT_DESC, SORT_RANK };
+static int g_last_sort_gpu = 0;
+int rfx_last_sort_on_gpu(void) { return g_last_sort_gpu; }
+
+static obj_p sort_host(int f, obj_p x, obj_p y, const char *why) {
+    g_last_sort_gpu = 0;
+    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
+    if (H.bound == 1 && H.f[f]) return y ? HOST_CALL(((rfx_binary_f)H.f[f])(x, y)) : HOST_CALL(((rfx_unary_f)H.f[f])(x));
+    char b[256];
+    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%s) and no host function to delegate to", HOST_FN[f] + 4, why);
+    return fail(b);
+}
+/* device scratch of this call: released by op_end() with the transients */
+static int sort_tmp(void **d, size_t bytes) {
+    if (g_noptmp >= (int)(sizeof(g_optmp) / sizeof(g_optmp[0]))) return RFX_ELIMIT;
+    int rc = rfx_hip_malloc(g_ctx, d, bytes ? bytes : 8);
+    if (rc == RFX_OK) g_optmp[g_noptmp++] = *d;
+    return rc;
+}
+static int sort_key_type(obj_p c) { return c->type == RFX_TYPE_I64 || c->type == RFX_TYPE_TIMESTAMP || c->type == RFX_TYPE_F64; }
+/* 0..n-1 (attrs ASC | DISTINCT) or n-1..0 (DESC | DISTINCT): the order of a vector whose attribute says it is sorted already */
+static obj_p sort_iota(int64_t n, int down) {
+    obj_p o = H.vector(RFX_TYPE_I64, n);
+    for (int64_t i = 0; i < n; i++) RFX_AS_I64(o)[i] = down ? n - 1 - i : i;
+    o->attrs = (uint8_t)((down ? ATTR_DESC_ : ATTR_ASC_) | ATTR_DISTINCT_);
+    return o;
+}
+static obj_p sort_reversed(obj_p x) { /* ray_reverse (core/compose.c:144-202): ATTR_ASC and ATTR_DESC change places, the other attributes stay */
+    obj_p o = H.vector(x->type, x->len);
+    for (int64_t i = 0; i < x->len; i++) RFX_AS_I64(o)[i] = RFX_AS_I64(x)[x->len - 1 - i];
+    o->attrs = (uint8_t)((x->attrs & ~(ATTR_ASC_ | ATTR_DESC_)) | ((x->attrs & ATTR_ASC_) ? ATTR_DESC_ : 0) | ((x->attrs & ATTR_DESC_) ? ATTR_ASC_ : 0));
+    return o;
+}
+static obj_p sort_unary(int kind, int f, obj_p x) {
+    rfx_host_bind();
+    if (!x) return fail("sort: null argument");
+    if (!(x->type > 0 && sort_key_type(x))) return sort_host(f, x, NULL, "key type");
+    const int64_t n = x->len;
+    const int desc = kind == SORT_IDESC || kind == SORT_DESC, values = kind == SORT_ASC || kind == SORT_DESC;
+    const int sorted_up = x->attrs & ATTR_ASC_, sorted_down = x->attrs & ATTR_DESC_;
+    const uint8_t out_attrs = values ? (uint8_t)((desc ? ATTR_DESC_ : ATTR_ASC_) | (x->attrs & ATTR_DISTINCT_)) : 0;
+    g_last_sort_gpu = 0;
+    /* the attribute is trusted, not the data (core/sort.c:430-451,691-712; core/order.c:79-83,165-169,524-538) */
+    if (values) {
+        if (desc ? sorted_down : sorted_up) return H.clone(x);
+        if (desc ? sorted_up : sorted_down) return sort_reversed(x);
+    } else if (kind == SORT_RANK) {
+        if (sorted_up) return sort_iota(n, 0); /* (ray_til: attrs ASC | DISTINCT) */
+        if (sorted_down) {
+            obj_p o = sort_iota(n, 1);
+            o->attrs = 0;
+            return o;
+        }
+    }
+    if (n == 0) {
+        obj_p o = H.vector(values ? x->type : RFX_TYPE_I64, 0);
+        o->attrs = out_attrs;
+        return o;
+    }
+    if (!values && kind != SORT_RANK) {
+        if (desc ? sorted_down : sorted_up) return sort_iota(n, 0);
+        if (desc ? sorted_up : sorted_down) return sort_iota(n, 1);
+    }
+    if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
+    if (g_nshards > 1) return sort_host(f, x, NULL, "sort over a sharded table");
+    const void *dv = NULL;
+    void *d0 = NULL, *d1 = NULL;
+    if (resident(x, 0, &dv) != RFX_OK) return fail_hip("column upload");
+    int rc = sort_tmp(&d0, (size_t)n * 8);
+    if (rc == RFX_OK && kind == SORT_RANK) rc = sort_tmp(&d1, (size_t)n * 8);
+    if (rc == RFX_OK) {
+        const void *cols[1] = {dv};
+        const int32_t types[1] = {col_ctype(x)};
+        if (values) rc = rfx_exec_sort_values(g_x, dv, types[0], desc, n, d0, NULL);
+        else rc = rfx_exec_sort(g_x, cols, types, 1, desc, n, (int64_t *)d0);
+        if (rc == RFX_OK && kind == SORT_RANK) rc = rfx_hip_inverse_perm(g_ctx, (const int64_t *)d0, n, (int64_t *)d1);
+    }
+    if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, x, NULL, rc == RFX_ENOMEM ? "device memory" : "more rows than the device sort takes");
+    if (rc != RFX_OK) return fail_hip("sort");
+    obj_p out = H.vector(values ? x->type : RFX_TYPE_I64, n);
+    if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), kind == SORT_RANK ? d1 : d0, (size_t)n * 8) != RFX_OK) {
+        H.drop(out);
+        return fail_hip("sort result");
+    }
+    out->attrs = out_attrs;
+    g_last_sort_gpu = 1;
+    return out;
+}
+static obj_p sort_table(int desc, int f, obj_p t, obj_p y) {
+    rfx_host_bind();
+    if (!t || !y) return fail("sort: null argument");
+    g_last_sort_gpu = 0;
+    if (t->type != RFX_TYPE_TABLE) return sort_host(f, t, y, "not a table");
+    if ((y->type == RFX_TYPE_SYMBOL || y->type == RFX_TYPE_I64) && y->len == 0) return H.clone(t); /* an empty symbol vector or [] */
+    if (y->type != -RFX_TYPE_SYMBOL && y->type != RFX_TYPE_SYMBOL) return sort_host(f, t, y, "sort columns are not symbols");
+    if (is_parted_table(t)) return sort_host(f, t, y, "parted table");
+    obj_p names = RFX_AS_LIST(t)[0], cols = RFX_AS_LIST(t)[1];
+    const int ncol = (int)cols->len, nk = y->type < 0 ? 1 : (int)y->len;
+    if (ncol < 1 || ncol > 64 || nk > 16) return sort_host(f, t, y, "too many columns");
+    const int64_t n = RFX_AS_LIST(cols)[0]->len;
+    for (int i = 0; i < ncol; i++) {
+        obj_p c = RFX_AS_LIST(cols)[i];
+        if (!(c->type > 0 && col_ctype(c)) || c->len != n) return sort_host(f, t, y, "a column that is not an 8-byte vector");
+    }
+    obj_p kc[16];
+    for (int k = 0; k < nk; k++) {
+        kc[k] = table_col(t, y->type < 0 ? y->i64 : RFX_AS_I64(y)[k]);
+        if (!kc[k]) return sort_host(f, t, y, "no such column");
+        if (!sort_key_type(kc[k])) return sort_host(f, t, y, "key type");
+    }
+    if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
+    if (g_nshards > 1) return sort_host(f, t, y, "sort over a sharded table");
+    const void *dperm = NULL;
+    obj_p hperm = NULL;
+    int on_gpu = 0;
+    if (n > 0 && y->type < 0 && (kc[0]->attrs & (ATTR_ASC_ | ATTR_DESC_))) { /* (one symbol: ray_iasc / ray_idesc of the column itself, attribute and all) */
+        const int up = (kc[0]->attrs & ATTR_ASC_) != 0;
+        hperm = sort_iota(n, desc ? up : !up);
+        if (transient(hperm, &dperm) != RFX_OK) {
+            H.drop(hperm);
+            return fail_hip("upload");
+        }
+    } else if (n > 0) {
+        const void *dk[16];
+        int32_t types[16];
+        void *d = NULL;
+        for (int k = 0; k < nk; k++) {
+            if (resident(kc[k], 0, &dk[k]) != RFX_OK) return fail_hip("column upload");
+            types[k] = col_ctype(kc[k]);
+        }
+        int rc = sort_tmp(&d, (size_t)n * 8);
+        if (rc == RFX_OK) rc = rfx_exec_sort(g_x, dk, types, nk, desc, n, (int64_t *)d);
+        if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, t, y, rc == RFX_ENOMEM ? "device memory" : "more rows than the device sort takes");
+        if (rc != RFX_OK) return fail_hip("sort");
+        dperm = d;
+        on_gpu = 1;
+    }
+    /* every column by the final permutation, RFX_MAX_KEYS columns per launch */
+    obj_p rv = H.vector(RFX_TYPE_LIST, ncol);
+    for (int i = 0; i < ncol; i++) RFX_AS_LIST(rv)[i] = NULL;
+    int ok = 1;
+    for (int c0 = 0; c0 < ncol && ok && n > 0; c0 += RFX_MAX_KEYS) {
+        const int m = ncol - c0 < RFX_MAX_KEYS ? ncol - c0 : RFX_MAX_KEYS;
+        const void *src[RFX_MAX_KEYS];
+        void *dst[RFX_MAX_KEYS];
+        void *block = NULL;
+        ok = rfx_hip_malloc(g_ctx, &block, (size_t)m * (size_t)n * 8) == RFX_OK;
+        for (int j = 0; j < m && ok; j++) {
+            ok = resident(RFX_AS_LIST(cols)[c0 + j], 0, &src[j]) == RFX_OK;
+            dst[j] = (char *)block + (size_t)j * (size_t)n * 8;
+        }
+        ok = ok && rfx_hip_gather_many(g_ctx, src, m, (const int64_t *)dperm, n, dst) == RFX_OK;
+        for (int j = 0; j < m && ok; j++) {
+            obj_p o = H.vector(RFX_AS_LIST(cols)[c0 + j]->type, n);
+            RFX_AS_LIST(rv)[c0 + j] = o;
+            ok = rfx_hip_d2h(g_ctx, RFX_AS_RAW(o), dst[j], (size_t)n * 8) == RFX_OK;
+        }
+        if (block) {
+            rfx_hip_ctx_sync(g_ctx);
+            rfx_hip_free(g_ctx, block);
+        }
+    }
+    if (hperm) H.drop(hperm);
+    for (int i = 0; i < ncol; i++)
+        if (!RFX_AS_LIST(rv)[i]) RFX_AS_LIST(rv)[i] = H.vector(RFX_AS_LIST(cols)[i]->type, 0); /* (an empty table, or the cells a failure left) */
+    if (!ok) {
+        H.drop(rv);
+        return fail_hip("sort: gather");
+    }
+    g_last_sort_gpu = on_gpu;
+    return H.table(H.clone(names), rv);
+}
+#define SORT_UNARY(name, kind, f)          \
+    rfx_obj_p name(rfx_obj_p x) {          \
+        op_begin();                        \
+        obj_p r = sort_unary(kind, f, x);  \
+        op_end();                          \
+        return r;                          \
+    }
+SORT_UNARY(rfx_iasc, SORT_IASC, F_IASC)
+SORT_UNARY(rfx_idesc, SORT_IDESC, F_IDESC)
+SORT_UNARY(rfx_asc, SORT_ASC, F_ASC)
+SORT_UNARY(rfx_desc, SORT_DESC, F_DESC)
+SORT_UNARY(rfx_rank, SORT_RANK, F_RANK)
+rfx_obj_p rfx_xasc(rfx_obj_p t, rfx_obj_p y) {
+    op_begin();
+    obj_p r = sort_table(0, F_XASC, t, y);
+    op_end();
+    return r;
+}
+rfx_obj_p rfx_xdesc(rfx_obj_p t, rfx_obj_p y) {
+    op_begin();
+    obj_p r = sort_table(1, F_XDESC, t, y);
+    op_end();
+    return r;
+}

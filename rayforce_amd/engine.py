@@ -342,6 +342,28 @@ class Engine:
         L.check(self.lib.rfx_hip_gather(self._ctx, col.data_ptr(), ids.data_ptr(), ids.numel(), out.data_ptr()), "gather")
         return out
 
+    def sort_index(self, columns, descending: bool = False) -> torch.Tensor:
+        """The stable order of the rows by ``columns`` (one i64 / f64 device column or a sequence, the first most significant; all
+        ascending or all descending) as an i64 device column: iasc / idesc, and the permutation behind xasc / xdesc (rfx_exec_sort)."""
+        cols = [columns] if isinstance(columns, torch.Tensor) else list(columns)
+        if not cols:
+            raise RfxError("sort_index needs at least one column")
+        n = cols[0].numel()
+        for c in cols:
+            self._check_col(c, n)
+        types = (C.c_int32 * len(cols))(*[_ctype_of(c) for c in cols])
+        ptrs = (C.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
+        out = torch.empty(n, dtype=torch.int64, device=self.device)
+        self._xcheck(self.lib.rfx_exec_sort(self._x, ptrs, types, len(cols), int(bool(descending)), n, out.data_ptr()), "sort")
+        return out
+
+    def sort_values(self, col: torch.Tensor, descending: bool = False) -> torch.Tensor:
+        """asc / desc: the column's own cells in sorted order (rfx_exec_sort_values)."""
+        self._check_col(col)
+        out = torch.empty_like(col)
+        self._xcheck(self.lib.rfx_exec_sort_values(self._x, col.data_ptr(), _ctype_of(col), int(bool(descending)), col.numel(), out.data_ptr(), None), "sort")
+        return out
+
     def eval_expr(self, expr, table=None) -> torch.Tensor:
         """``(op x y)`` / an expression tree over columns and atoms as a device column: ray_add .. ray_mod (binop_map,
         core/math.c:2280-2345) in ONE pass whatever the depth."""
