@@ -205,6 +205,23 @@ int rfx_exec_join_index(rfx_exec_t *x, const void *const *d_left_keys, const voi
  * table and probes its own rows: no exchange.  To be called on the shard's thread (rfx_exec_run). */
 int rfx_exec_join_index_shard(rfx_exec_t *x, int shard, const void *const *dlk, const void *const *drk, int nk, int64_t nl, int64_t nr, int64_t *d_ids, int *collision);
 
+/* ---- asof join index, bin, binr (rfx_asof.hip): one shard only (RFX_ELIMIT "asof join over a sharded table" / "bin over a sharded table") ----
+ * rfx_exec_asof_index (index_asof_join_obj, core/index.c:3194-3267): the right rows are grouped by their key tuple (nkeys 8-byte integer columns,
+ * cells compared as raw integers: null equals null), every group's rows kept in ascending ROW order; d_ids[i] = the row the reference's
+ * closed-interval binary search over left row i's group lands on -- last probe with d_right_time[row] <= d_left_time[i] -- or null (no group,
+ * or no probe qualified).  Times are signed 64-bit integers (I64 / TIMESTAMP, or I32 / DATE / TIME widened), a null the smallest; the right
+ * times need not be sorted, and then the probe sequence decides (see rfx_hip_seg_search).
+ * BUILD: the equi-join index of the right keys against themselves (every right row's group = its group's first row), one stable sort of those
+ * ids, the run boundaries, the right times gathered into group order.  PROBE: the equi-join index of the left keys against the right keys, then
+ * one search per left row.  Scratch 48 B per right row + the sort's 24 B + the join index's, freed before return; RFX_ENOMEM when it does not fit,
+ * RFX_ELIMIT above 2^32 - 1 right rows.  RFX_ESTATE with *collision = 1 as for rfx_exec_join_index.
+ * rfx_exec_bin (ray_bin / ray_binr, core/items.c:1399-1644): d_out[j] = the search of d_y[j] over the whole of d_x by position -- right = 0: last
+ * probe with x[mid] <= y, none = -1; right = 1: first probe with x[mid] >= y, none = nx.
+ * RFX_XSTAT_ASOF_JOINS / _BINS / _SEARCHES count what ran, RFX_XSTAT_NS_ASOF_BUILD / _PROBE the two halves' wall time. */
+int rfx_exec_asof_index(rfx_exec_t *x, const void *const *d_left_keys, const void *const *d_right_keys, int nkeys, const int64_t *d_left_time,
+                        const int64_t *d_right_time, int64_t nleft, int64_t nright, int64_t *d_ids, int *collision);
+int rfx_exec_bin(rfx_exec_t *x, const int64_t *d_x, int64_t nx, const int64_t *d_y, int64_t ny, int right, int64_t *d_out);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -231,7 +248,12 @@ enum {
     RFX_XSTAT_NS_TOTAL = 15,     /* rfx_exec_group_by entry to exit, + the fetches */
     RFX_XSTAT_SORTS = 16,        /* sorts (one per key column of a multi-column sort) answered by the device path */
     RFX_XSTAT_SORT_PASSES = 17,  /* ... radix passes they executed (a digit every key agrees on costs none) */
-    RFX_XSTAT_N = 18
+    RFX_XSTAT_ASOF_JOINS = 18,   /* asof join indexes answered by the device path */
+    RFX_XSTAT_BINS = 19,         /* bin / binr calls answered by the device path */
+    RFX_XSTAT_SEARCHES = 20,     /* ... binary searches those two ran (left rows of an asof join with a right side, cells of a bin / binr) */
+    RFX_XSTAT_NS_ASOF_BUILD = 21, /* wall time of the asof joins' build halves (right side only), nanoseconds, to the stream idle */
+    RFX_XSTAT_NS_ASOF_PROBE = 22, /* ... and of their probe halves */
+    RFX_XSTAT_N = 23
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

@@ -660,6 +660,22 @@ int rfx_hip_sort_index(rfx_ctx_t *ctx, const void *d_col, int32_t type, int64_t 
 int rfx_hip_sort_values(rfx_ctx_t *ctx, const void *d_col, int32_t type, int64_t n, int descending, void *d_out, int64_t *d_perm_out, int32_t *passes);
 int rfx_hip_inverse_perm(rfx_ctx_t *ctx, const int64_t *d_perm, int64_t n, int64_t *d_out);
 
+/* ---- segmented binary search (rfx_asof.hip): asof-join, bin, binr (index_bin_i64 core/index.c:3121-3137, core/items.c:1399-1644) ----
+ * The reference's closed-interval loop, step for step -- left = 0, right = len - 1; mid = left + (right - left) / 2 -- because the searched
+ * cells need not be sorted and then the probe sequence IS the answer.  right = 0: the last probe position with t[mid] <= q ("<=-last": asof,
+ * bin); right = 1: the first probe position with t[mid] >= q (">=-first": binr).  Cells compare as signed 64-bit integers (a null is the
+ * smallest value).
+ * rfx_hip_seg_search: query i searches ONE contiguous segment of d_t:
+ *   d_group == NULL: d_t[0 .. len) for every query;
+ *   else segment d_seg[2 g] .. d_seg[2 g + 1] (start, one past the end) for g = d_group[i]; g outside [0, ngroups) -- a null -- has no segment.
+ *   d_out[i] = `none` when no probe qualified (or no segment), else the position inside the segment, or d_rows[start + position] with d_rows.
+ *   d_out may be d_group itself; it may alias nothing else.
+ * rfx_hip_asof_runs: d_sorted_groups[0 .. n) holds group ids in [0, n) with equal ids adjacent; d_seg (2 n cells) receives, at the id of
+ *   every group that occurs, its run's start and end.  The other cells are left as they were. */
+int rfx_hip_seg_search(rfx_ctx_t *ctx, const int64_t *d_q, int64_t n, const int64_t *d_group, int64_t ngroups, const int64_t *d_seg, int64_t len,
+                       const int64_t *d_t, const int64_t *d_rows, int right, int64_t none, int64_t *d_out);
+int rfx_hip_asof_runs(rfx_ctx_t *ctx, const int64_t *d_sorted_groups, int64_t n, int64_t *d_seg);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -35,6 +35,8 @@
  *   rfx_asc rfx_desc       ray_asc ray_desc      core/order.c:74-244             unary_f   -> the sorted cells, ATTR_ASC / ATTR_DESC
  *   rfx_rank               ray_rank              core/order.c:519-556            unary_f   -> the inverse of iasc
  *   rfx_xasc rfx_xdesc     ray_xasc ray_xdesc    core/order.c:246-420            binary_f  (table, column symbol | symbol vector) -> table
+ *   rfx_asof_join          ray_asof_join         core/join.c:300-356             vary_f    (key symbols, the last one the asof column; left table, right table)
+ *   rfx_bin rfx_binr       ray_bin ray_binr      core/items.c:1399-1644          binary_f  (I64 / TIMESTAMP vector, vector of the same type) -> I64 positions
  *
  * Everything below runs on the MI355X through the flat ABI of rfx_hip.h.  There is NO CPU implementation behind these
  * entry points: queries whose shape the GPU path does not cover are handed back to the host's own ray_* function when
@@ -138,6 +140,23 @@ rfx_obj_p rfx_xasc(rfx_obj_p t, rfx_obj_p cols);
 rfx_obj_p rfx_xdesc(rfx_obj_p t, rfx_obj_p cols);
 /* 1: the last of those seven calls ran the device sort; 0: it was answered from an attribute / an empty argument, or handed to the host */
 int rfx_last_sort_on_gpu(void);
+/* vary_f: (asof-join [k1 .. kn t] left right) -- ray_asof_join, core/join.c:300-356: for every left row the right row of the same k1 .. kn tuple that
+ * the reference's binary search by t over the tuple's rows (kept in ROW order; index_asof_join_obj, core/index.c:3194-3267) lands on -- on right
+ * times that ascend inside every tuple, the last one at or before the left row's time -- assembled as a left join (all key columns, t included,
+ * are the left table's own).  Right times that do not ascend are searched with the reference's very probe sequence, so the answers agree there too.
+ * On the device (rfx_asof.hip): 1..8 equality keys that are 8-byte integer columns of one type in both tables (I64 / SYMBOL / TIMESTAMP), an asof
+ * column of I64 / TIMESTAMP / I32 / DATE / TIME, every other column an 8-byte vector (the asof column is told by its NAME: its 4-byte vector under a
+ * second column name is such another column).  A right-only column's unmatched rows are typed nulls (as for
+ * rfx_left_join; the reference returns a LIST holding Null objects there).  Every other shape -- an F64 asof column, other key or column types,
+ * more than 64 columns, sharded columns, a row-hash collision, scratch that does not fit -- and every argument error is the host's own verb.
+ * binary_f: (bin x y) / (binr x y) -- ray_bin / ray_binr, core/items.c:1399-1644, of two I64 or two TIMESTAMP vectors: per cell of y the same search
+ * over the whole of x by position -- bin: the last probe with x[mid] <= y, else -1; binr: the first probe with x[mid] >= y, else len x -- as an I64
+ * vector.  Atoms on the right, 4-byte vectors and every other pair of types are the host's own verb. */
+rfx_obj_p rfx_asof_join(rfx_obj_p *x, int64_t n);
+rfx_obj_p rfx_bin(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_binr(rfx_obj_p x, rfx_obj_p y);
+/* 1: the last of those three calls ran the device search; 0: it had no row to search for (an empty left table, an empty y), or went to the host */
+int rfx_last_asof_on_gpu(void);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

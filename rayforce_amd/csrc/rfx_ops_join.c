@@ -147,13 +147,68 @@ done:
     return rcode;
 }
 
+/* result columns: keys, then the other left columns, then the right-only ones (ray_union / ray_except order, core/join.c:83-156); at most 64 are
+ * collected (64 back = more than this path takes) */
+static int join_column_names(obj_p ksyms, obj_p lt, obj_p rt, int64_t *names) {
+    int ncol = 0;
+    for (int64_t i = 0; i < ksyms->len && ncol < 64; i++) names[ncol++] = RFX_AS_I64(ksyms)[i];
+    for (int pass = 0; pass < 2; pass++) {
+        obj_p nm = RFX_AS_LIST(pass ? rt : lt)[0];
+        for (int64_t i = 0; i < nm->len && ncol < 64; i++) {
+            int64_t sy = RFX_AS_I64(nm)[i];
+            int dup = 0;
+            for (int j = 0; j < ncol; j++) dup |= names[j] == sy;
+            if (!dup) names[ncol++] = sy;
+        }
+    }
+    return ncol;
+}
+/* The table of a left join from its index (__left_join_inner, core/join.c:83-156, which the reference shares between left-join and asof-join):
+ * ids = per left row a right row or null, on the device.  The key columns (all of ksyms) and the left-only columns are the left table's own
+ * objects; a column the right table has takes the matched right row's cell, else the left row's own, else the typed null.
+ * 1: *res is the table; 0: more columns than this path takes (the caller hands the join over); -1: failed, *res is the error object. */
+static int left_join_assemble(obj_p ksyms, obj_p lt, obj_p rt, const void *ids, int64_t nl, obj_p *res) {
+    int64_t names[64];
+    const int nk = (int)ksyms->len, ncol = join_column_names(ksyms, lt, rt, names);
+    if (ncol >= 64) return 0;
+    void *dcol = NULL;
+    if (rfx_hip_malloc(g_ctx, &dcol, (size_t)(nl ? nl : 1) * 8) != RFX_OK) { *res = fail_hip("join scratch"); return -1; }
+    obj_p rk_ = H.vector(RFX_TYPE_SYMBOL, ncol), rv = H.vector(RFX_TYPE_LIST, ncol);
+    int ok = 1;
+    for (int c = 0; c < ncol; c++) {
+        RFX_AS_I64(rk_)[c] = names[c];
+        obj_p lc = table_col(lt, names[c]), rc = table_col(rt, names[c]);
+        obj_p o = NULL;
+        if (c < nk || !rc) o = H.clone(lc);
+        else if (!col_ctype(rc) || (lc && !col_ctype(lc))) { /* (the callers' checks keep such columns out: never write 8-byte cells into a narrower vector) */
+            o = H.vector(rc->type, 0);
+            ok = 0;
+        } else {
+            o = H.vector(rc->type, nl);
+            const void *dsrc, *dleft = NULL;
+            ok = ok && resident(rc, 0, &dsrc) == RFX_OK;
+            if (ok && lc) ok = resident(lc, 0, &dleft) == RFX_OK;
+            if (ok && nl) {
+                ok = rfx_hip_gather_or(g_ctx, dsrc, dleft, (const int64_t *)ids, nl, col_ctype(rc) == RFX_F64 ? 0x7FF8000000000000ull : 0x8000000000000000ull, dcol) == RFX_OK;
+                ok = ok && rfx_hip_d2h(g_ctx, RFX_AS_RAW(o), dcol, (size_t)nl * 8) == RFX_OK;
+            }
+        }
+        RFX_AS_LIST(rv)[c] = o;
+    }
+    if (ok) *res = H.table(rk_, rv);
+    else { H.drop(rk_); H.drop(rv); *res = fail_hip("join columns"); }
+    rfx_hip_ctx_sync(g_ctx);
+    rfx_hip_free(g_ctx, dcol);
+    return ok ? 1 : -1;
+}
+
 static obj_p join_impl(int inner, obj_p *x, int64_t n) {
     rfx_host_bind();
     const int fidx = inner ? F_IJ : F_LJ;
     if (n != 3 || !x[0] || !x[1] || !x[2]) return fail("join: expected (keys, left table, right table)");
     if (x[0]->type != RFX_TYPE_SYMBOL || x[1]->type != RFX_TYPE_TABLE || x[2]->type != RFX_TYPE_TABLE) return fail("join: expected (symbol vector, table, table)");
     obj_p ksyms = x[0], lt = x[1], rt = x[2];
-    obj_p lnames = RFX_AS_LIST(lt)[0], lcols = RFX_AS_LIST(lt)[1], rnames = RFX_AS_LIST(rt)[0], rcols = RFX_AS_LIST(rt)[1];
+    obj_p lcols = RFX_AS_LIST(lt)[1], rnames = RFX_AS_LIST(rt)[0], rcols = RFX_AS_LIST(rt)[1];
     const int64_t nl = lcols->len ? RFX_AS_LIST(lcols)[0]->len : 0, nr = rcols->len ? RFX_AS_LIST(rcols)[0]->len : 0;
     const int nk = (int)ksyms->len;
     const char *why = NULL;
@@ -197,24 +252,20 @@ static obj_p join_impl(int inner, obj_p *x, int64_t n) {
         if (jrc != RFX_OK && collision) { why = "row-hash collision between two key tuples"; goto out; }
         if (jrc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
     }
-    /* result columns: keys, then the other left columns, then the right-only ones (ray_union / ray_except order, core/join.c:83-156) */
+    if (!inner) {
+        const int a = left_join_assemble(ksyms, lt, rt, ids, nl, &res);
+        if (a == 0) { why = "too many columns"; goto out; }
+        if (a > 0) g_last_gpu = 1;
+        goto done;
+    }
+    /* inner join: the matched left rows in order, paired with their right rows (index_inner_join_obj); columns in the left join's order */
     {
         int64_t names[64];
-        int ncol = 0;
-        for (int i = 0; i < nk; i++) names[ncol++] = RFX_AS_I64(ksyms)[i];
-        for (int pass = 0; pass < 2; pass++) {
-            obj_p nm = pass ? rnames : lnames;
-            for (int64_t i = 0; i < nm->len && ncol < 64; i++) {
-                int64_t sy = RFX_AS_I64(nm)[i];
-                int dup = 0;
-                for (int j = 0; j < ncol; j++) dup |= names[j] == sy;
-                if (!dup) names[ncol++] = sy;
-            }
-        }
+        const int ncol = join_column_names(ksyms, lt, rt, names);
         if (ncol >= 64) { why = "too many columns"; goto out; }
         void *lids = NULL, *rids = NULL, *dcol = NULL;
         int64_t nout = nl;
-        if (inner) { /* matched left rows in order, paired with their right rows (index_inner_join_obj) */
+        {
             rfx_pred_t p;
             memset(&p, 0, sizeof(p));
             p.d_col = ids; p.col_type = RFX_I64; p.op = RFX_NE; p.rhs_type = RFX_I64; p.rhs_i = RFX_NULL_I64;
@@ -229,20 +280,13 @@ static obj_p join_impl(int inner, obj_p *x, int64_t n) {
         for (int c = 0; c < ncol; c++) {
             RFX_AS_I64(rk_)[c] = names[c];
             obj_p lc = table_col(lt, names[c]), rc = table_col(rt, names[c]);
-            const int iskey = c < nk;
-            obj_p o = NULL;
-            if (!inner && (iskey || !rc)) o = H.clone(lc); /* left join: key columns and left-only columns are the left table's own */
-            else {
-                obj_p src = (inner ? (rc ? rc : lc) : rc);
-                o = H.vector(src->type, nout);
-                const void *dsrc, *dleft = NULL;
-                ok = ok && resident(src, 0, &dsrc) == RFX_OK;
-                if (ok && !inner && lc) ok = resident(lc, 0, &dleft) == RFX_OK;
-                if (ok && nout) {
-                    if (inner) ok = rfx_hip_gather(g_ctx, dsrc, (const int64_t *)(rc ? rids : lids), nout, dcol) == RFX_OK;
-                    else ok = rfx_hip_gather_or(g_ctx, dsrc, dleft, (const int64_t *)ids, nout, col_ctype(src) == RFX_F64 ? 0x7FF8000000000000ull : 0x8000000000000000ull, dcol) == RFX_OK;
-                    ok = ok && rfx_hip_d2h(g_ctx, RFX_AS_RAW(o), dcol, (size_t)nout * 8) == RFX_OK;
-                }
+            obj_p src = rc ? rc : lc;
+            obj_p o = H.vector(src->type, nout);
+            const void *dsrc;
+            ok = ok && resident(src, 0, &dsrc) == RFX_OK;
+            if (ok && nout) {
+                ok = rfx_hip_gather(g_ctx, dsrc, (const int64_t *)(rc ? rids : lids), nout, dcol) == RFX_OK;
+                ok = ok && rfx_hip_d2h(g_ctx, RFX_AS_RAW(o), dcol, (size_t)nout * 8) == RFX_OK;
             }
             RFX_AS_LIST(rv)[c] = o;
         }

@@ -442,6 +442,26 @@ class Engine:
         from . import joins
         return joins.inner_join(self, keys, left, right)
 
+    def asof_index(self, keys, time, left, right) -> torch.Tensor:
+        """Per left row the right row an asof join pairs it with, or null (rfx_exec_asof_index)."""
+        from . import joins
+        return joins.asof_index(self, keys, time, left, right)
+
+    def asof_join(self, keys, left, right) -> Dict[str, torch.Tensor]:
+        """``(asof-join keys left right)``: the last of ``keys`` is the asof column."""
+        from . import joins
+        return joins.asof_join(self, keys, left, right)
+
+    def bin(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``(bin x y)``: per cell of y the last probe position of the reference's binary search with x[mid] <= y, else -1."""
+        from . import joins
+        return joins.bin_search(self, x, y, False)
+
+    def binr(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``(binr x y)``: the first probe position with x[mid] >= y, else len x."""
+        from . import joins
+        return joins.bin_search(self, x, y, True)
+
     # ------------------------------------------------------------------ the select surface (core/query.c:607-654)
     def select(self, query: Dict) -> Dict[str, torch.Tensor]:
         """``(select {name: (fn col) ... from: t where: p by: k})`` with t a dict of equally long device columns -- answered by the planner

@@ -42,6 +42,10 @@ OPS_PROTOTYPES = {
     "rfx_xasc": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_xdesc": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_last_sort_on_gpu": (C.c_int, []),
+    "rfx_asof_join": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
+    "rfx_bin": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "rfx_binr": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "rfx_last_asof_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),

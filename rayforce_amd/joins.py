@@ -76,3 +76,61 @@ def inner_join(eng, keys, left: Dict[str, torch.Tensor], right: Dict[str, torch.
             out[name] = eng.at_ids(left[name], lids)
     return out
 
+
+def asof_index(eng, keys, time, left: Dict[str, torch.Tensor], right: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """Per LEFT row the right row of the same ``keys`` tuple that the reference's binary search by ``time`` over the tuple's rows (in row
+    order) lands on, or null (index_asof_join_obj, core/index.c:3194-3267): the planner's rfx_exec_asof_index.  i64 columns throughout."""
+    keys = [keys] if isinstance(keys, str) else list(keys)
+    if not keys:
+        raise RfxError("asof_index needs at least one equality key")
+    lk = [eng._check_col(eng._resolve(k, left)) for k in keys]
+    rk = [eng._check_col(eng._resolve(k, right)) for k in keys]
+    nl, nr = lk[0].numel(), rk[0].numel()
+    lt, rt = eng._check_col(eng._resolve(time, left), nl), eng._check_col(eng._resolve(time, right), nr)
+    if any(c.dtype != torch.int64 for c in lk + rk + [lt, rt]):
+        raise RfxError("asof keys and times must be i64-like columns on this path")
+    ids = eng.empty(nl)
+    k = len(keys)
+    col = C.c_int(0)
+    rc = eng.lib.rfx_exec_asof_index(eng._x, (C.c_void_p * k)(*[c.data_ptr() for c in lk]), (C.c_void_p * k)(*[c.data_ptr() for c in rk]), k,
+                                      lt.data_ptr(), rt.data_ptr(), nl, nr, ids.data_ptr(), C.byref(col))
+    if rc != L.RFX_OK and col.value:
+        raise RfxError("asof join: two key tuples share one 64-bit row hash (collision); not answered on this path")
+    eng._xcheck(rc, "asof_index")
+    return ids
+
+def asof_join(eng, keys, left: Dict[str, torch.Tensor], right: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """``(asof-join [k1 .. kn t] left right)`` -- ray_asof_join, core/join.c:300-356: ``keys`` names the equality columns and, last, the asof
+    column; the result is the left join's (all key columns are the left table's own; no empty-table short-cut)."""
+    keys = list(keys)
+    if len(keys) < 2:
+        raise RfxError("asof_join needs at least one equality key and the asof column")
+    nl = next(iter(left.values())).numel() if left else 0
+    ids = asof_index(eng, keys[:-1], keys[-1], left, right)
+    out = {k: left[k] for k in keys}
+    for name in [c for c in left if c not in keys] + [c for c in right if c not in keys and c not in left]:
+        if name not in right:
+            out[name] = left[name]
+            continue
+        rc, lc = right[name], left.get(name)
+        if lc is not None and lc.dtype != rc.dtype:
+            raise RfxError(f"join: column {name} has different types in the two tables")
+        o = torch.empty(nl, dtype=rc.dtype, device=eng.device)
+        fill = 0x7FF8000000000000 if rc.dtype == torch.float64 else (1 << 63)  # NaN / NULL_I64 bit patterns
+        if rc.numel() == 0:  # (nothing to read from: every id is null)
+            rc = torch.empty(1, dtype=rc.dtype, device=eng.device)
+        L.check(eng.lib.rfx_hip_gather_or(eng._ctx, rc.data_ptr(), lc.data_ptr() if lc is not None else None, ids.data_ptr(), nl, fill, o.data_ptr()), "gather_or")
+        out[name] = o
+    eng.sync()
+    return out
+
+def bin_search(eng, x: torch.Tensor, y: torch.Tensor, right: bool) -> torch.Tensor:
+    """bin (right = False) / binr (True) of two i64 device columns: rfx_exec_bin."""
+    eng._check_col(x)
+    eng._check_col(y)
+    if x.dtype != torch.int64 or y.dtype != torch.int64:
+        raise RfxError("bin / binr take i64-like columns on this path")
+    out = eng.empty(y.numel())
+    eng._xcheck(eng.lib.rfx_exec_bin(eng._x, x.data_ptr(), x.numel(), y.data_ptr(), y.numel(), int(bool(right)), out.data_ptr()), "bin")
+    eng.sync()
+    return out
