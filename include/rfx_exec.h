@@ -222,6 +222,26 @@ int rfx_exec_asof_index(rfx_exec_t *x, const void *const *d_left_keys, const voi
                         const int64_t *d_right_time, int64_t nleft, int64_t nright, int64_t *d_ids, int *collision);
 int rfx_exec_bin(rfx_exec_t *x, const int64_t *d_x, int64_t nx, const int64_t *d_y, int64_t ny, int right, int64_t *d_out);
 
+/* ---- window join (rfx_window.hip): one shard only (RFX_ELIMIT "window join over a sharded table") ----
+ * rfx_exec_window_ranges (index_window_join_obj, core/index.c:3269-3347, and the searches of the INDEX_TYPE_WINDOW arms, core/aggr.c:133-160):
+ * d_perm (nright cells) = the right rows in the stable order of (key tuple, d_right_time) -- the tuples' groups contiguous, in the order of their
+ * first rows (the reference's xasc orders them by key; nothing downstream depends on the order of the groups); per left row i (d_li[i], d_ri[i])
+ * = the first and last POSITION in that order of its window [d_left_lo[i], d_left_hi[i]] over its tuple's group, or (-1, -2) for the null row
+ * (no group, or the reference's null tests).  closed = 0: window-join (the row prevailing at the window's start is inside); 1: window-join1.
+ * Keys are 8-byte integer columns compared as raw integers (null equals null); times and bounds are signed 64-bit cells holding 32-bit values
+ * (I32 / DATE / TIME widened, a null the smallest).  stats (host, 2 cells, may be NULL): windows longer than 16 rows, the longest window.
+ * BUILD: the equi-join index of the right keys against themselves, one two-column stable sort, the run boundaries, the times gathered.
+ * PROBE: the equi-join index of the left keys against the right keys, two searches per left row.  Scratch 56 B per right row + 8 B per left
+ * row + the sort's and the join index's, freed before return.  RFX_ENOMEM / RFX_ELIMIT / RFX_ESTATE with *collision = 1 as rfx_exec_asof_index.
+ * rfx_exec_window_fold: every aggregate of one value column (type RFX_I64 / RFX_F64, nright cells) over those windows in ONE launch.  d_perm:
+ * the permutation above -- the column is gathered into a scratch copy (8 B per right row) first -- or NULL when d_vals is in that order
+ * already.  d_outs: RFX_WAGG_N device pointers (include/rfx_hip.h), NULL = not wanted, nleft cells each.  long_windows: stats[0]. */
+int rfx_exec_window_ranges(rfx_exec_t *x, const void *const *d_left_keys, const void *const *d_right_keys, int nkeys, const int64_t *d_left_lo,
+                           const int64_t *d_left_hi, const int64_t *d_right_time, int64_t nleft, int64_t nright, int closed, int64_t *d_perm,
+                           int64_t *d_li, int64_t *d_ri, int64_t *stats, int *collision);
+int rfx_exec_window_fold(rfx_exec_t *x, const void *d_vals, int32_t type, const int64_t *d_perm, const int64_t *d_li, const int64_t *d_ri, int64_t nleft,
+                         int64_t nright, int64_t long_windows, void *const *d_outs);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */

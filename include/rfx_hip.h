@@ -676,6 +676,25 @@ int rfx_hip_seg_search(rfx_ctx_t *ctx, const int64_t *d_q, int64_t n, const int6
                        const int64_t *d_t, const int64_t *d_rows, int right, int64_t none, int64_t *d_out);
 int rfx_hip_asof_runs(rfx_ctx_t *ctx, const int64_t *d_sorted_groups, int64_t n, int64_t *d_seg);
 
+/* ---- window join (rfx_window.hip): window-join / window-join1 (core/join.c:358-489, the INDEX_TYPE_WINDOW arms of core/aggr.c) ----
+ * The right table sorted by (key tuple, time): d_t its times, d_seg the groups' runs as rfx_hip_asof_runs writes them, d_group per left row
+ * the id of its group (null: none).  Times and window bounds are 8-byte cells holding the reference's 4-byte ones widened (rfx_hip_widen_i32).
+ * rfx_hip_window_ranges: per left row the reference's two searches over its group (core/aggr.c:39-71) and its null tests:
+ *   d_ri[i] = the last position with t <= d_hi[i]; d_li[i] = the last position with t <= d_lo[i] (closed = 0, window-join) or the first with
+ *   t >= d_lo[i] (closed = 1, window-join1); a search that finds nothing answers the group's first position.  No group, t[li] > hi, or
+ *   (closed) t[ri] < lo: the null row, (d_li, d_ri) = (-1, -2).  d_stats (2 cells, zeroed by the caller) receives the number of windows longer
+ *   than 16 rows and the longest window.
+ * rfx_hip_window_fold: every aggregate of ONE value column (RFX_I64 / RFX_F64; nvals cells in the sorted order, 16-byte aligned) over rows
+ *   d_li[i] .. d_ri[i], in one launch: d_outs[RFX_WAGG_*] (7 pointers, NULL = not wanted) receive n cells each -- sum, min, max, first, last in
+ *   the column's type, count as i64, avg as f64 -- by the reference's rules: a null cell makes sum null; min / max / avg / first / last skip null
+ *   cells (no cell left: INT64_MAX / +inf for min, null for the others); count counts every row; the null row counts 0 and is null elsewhere.
+ *   long_windows: what rfx_hip_window_ranges counted (0: a lane per row; else a wave folds the long windows, and fewer rows go to a wave). */
+enum { RFX_WAGG_SUM = 0, RFX_WAGG_MIN = 1, RFX_WAGG_MAX = 2, RFX_WAGG_COUNT = 3, RFX_WAGG_AVG = 4, RFX_WAGG_FIRST = 5, RFX_WAGG_LAST = 6, RFX_WAGG_N = 7 };
+int rfx_hip_window_ranges(rfx_ctx_t *ctx, const int64_t *d_lo, const int64_t *d_hi, int64_t n, const int64_t *d_group, int64_t ngroups,
+                          const int64_t *d_seg, const int64_t *d_t, int closed, int64_t *d_li, int64_t *d_ri, uint64_t *d_stats);
+int rfx_hip_window_fold(rfx_ctx_t *ctx, const void *d_vals, int32_t type, int64_t nvals, const int64_t *d_li, const int64_t *d_ri, int64_t n,
+                        int64_t long_windows, void *const *d_outs);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -37,6 +37,7 @@
  *   rfx_xasc rfx_xdesc     ray_xasc ray_xdesc    core/order.c:246-420            binary_f  (table, column symbol | symbol vector) -> table
  *   rfx_asof_join          ray_asof_join         core/join.c:300-356             vary_f    (key symbols, the last one the asof column; left table, right table)
  *   rfx_bin rfx_binr       ray_bin ray_binr      core/items.c:1399-1644          binary_f  (I64 / TIMESTAMP vector, vector of the same type) -> I64 positions
+ *   rfx_window_join rfx_window_join1  ray_window_join ray_window_join1  core/join.c:358-489  vary_f  (key symbols, windows, left table, right table, aggregates)
  *
  * Everything below runs on the MI355X through the flat ABI of rfx_hip.h.  There is NO CPU implementation behind these
  * entry points: queries whose shape the GPU path does not cover are handed back to the host's own ray_* function when
@@ -157,6 +158,22 @@ rfx_obj_p rfx_bin(rfx_obj_p x, rfx_obj_p y);
 rfx_obj_p rfx_binr(rfx_obj_p x, rfx_obj_p y);
 /* 1: the last of those three calls ran the device search; 0: it had no row to search for (an empty left table, an empty y), or went to the host */
 int rfx_last_asof_on_gpu(void);
+/* vary_f: (window-join [k1 .. kn t] windows left right {name: (agg col) ...}) / (window-join1 ...) -- ray_window_join / ray_window_join1,
+ * core/join.c:358-489: `windows` is a LIST of two vectors, a lower and an upper bound of t per left row; every left row folds `agg` over the right
+ * rows of its k1 .. kn tuple, in order of t, from the row the reference's search finds for the lower bound -- window-join: the last with t <= lo, so
+ * the row prevailing at the window's start is inside; window-join1: the first with t >= lo -- to the last with t <= hi.  The result is the left
+ * table's columns followed by one column per dict entry (count: I64, avg: F64, else the column's type); a left row without a group, or whose
+ * window the reference's tests call empty, counts 0 and is null elsewhere.
+ * On the device (rfx_window.hip): 1..8 equality keys that are 8-byte integer columns of one type in both tables (I64 / SYMBOL / TIMESTAMP), a
+ * window column of TIME / DATE / I32 of one type in both tables, two 4-byte integer window vectors of the left table's length, aggregates of the
+ * form (agg col) with agg one of sum, min, max, count, avg, first, last (the function object or its name) and col an I64 or F64 column of the
+ * right table (at most 64 entries over 16 columns).  An empty left table is answered with empty typed columns.  Every other shape -- raw columns
+ * ({bids: Bid}), med / dev, nested expressions, other value types, an 8-byte window column, parted tables, sharded columns, a row-hash collision,
+ * scratch that does not fit -- and every argument error is the host's own verb. */
+rfx_obj_p rfx_window_join(rfx_obj_p *x, int64_t n);
+rfx_obj_p rfx_window_join1(rfx_obj_p *x, int64_t n);
+/* 1: the last of those two calls ran on the device; 0: its left table was empty, or it went to the host */
+int rfx_last_window_on_gpu(void);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

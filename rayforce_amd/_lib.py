@@ -119,6 +119,7 @@ RFX_XSTAT_SCOPE_SAMPLED, RFX_XSTAT_SCOPE_RETRIED, RFX_XSTAT_SCOPE_REMEMBERED, RF
     RFX_XSTAT_NS_EMIT, RFX_XSTAT_NS_FETCH, RFX_XSTAT_NS_TOTAL = range(16)
 RFX_XSTAT_SORTS, RFX_XSTAT_SORT_PASSES = 16, 17
 RFX_XSTAT_ASOF_JOINS, RFX_XSTAT_BINS, RFX_XSTAT_SEARCHES, RFX_XSTAT_NS_ASOF_BUILD, RFX_XSTAT_NS_ASOF_PROBE = 18, 19, 20, 21, 22
+RFX_WAGG = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "first": 5, "last": 6}  # include/rfx_hip.h RFX_WAGG_*
 RFX_XSTAT_PHASES = (("scope", 9), ("pass", 10), ("merge", 11), ("rank", 12), ("emit", 13), ("fetch", 14), ("total", 15))
 
 
@@ -277,6 +278,8 @@ PROTOTYPES = {
     "rfx_hip_inverse_perm": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_window_ranges": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rfx_hip_window_fold": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _P(C.c_void_p)]),
     "rfx_hip_eval_expr": (C.c_int, [_ctx, _P(Agg), C.c_int64, C.c_void_p, _P(C.c_int32)]),
     "rfx_hip_join_probe_dense": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "rfx_hip_join_probe_hash": (C.c_int, [_ctx, C.c_void_p, C.c_int64, _P(HashTables), C.c_void_p]),
@@ -339,6 +342,9 @@ EXEC_PROTOTYPES = {
     "rfx_exec_sort_values": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_bin": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                               C.c_void_p, C.c_void_p, _P(C.c_int64), _P(C.c_int)]),
+    "rfx_exec_window_fold": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_void_p)]),
     "rfx_exec_join_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_join_index_shard": (C.c_int, [_exec, C.c_int, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_stat": (C.c_int64, [_exec, C.c_int]),

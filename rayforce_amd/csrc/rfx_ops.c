@@ -51,15 +51,19 @@ static struct {
     /* the host's own built-ins, for recognising function objects inside parsed expressions and for delegation */
     void *f[48];
 } H;
-enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_N };
+/* F_SUM .. F_FIRST are the aggregates rfx_select / rfx_update map (they test that id RANGE); the ids after F_BINR are not: F_LAST is recognised by
+ * window_agg (rfx_ops_window.c) alone, and every other reader of fn_id must keep refusing it */
+enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_N };
 static const char *HOST_FN[F_N] = {"ray_sum", "ray_avg", "ray_min", "ray_max", "ray_count", "ray_first", "ray_eq",  "ray_ne",  "ray_lt",  "ray_gt",
                                    "ray_le",  "ray_ge",  "ray_and", "ray_or",  "ray_select", "ray_add",  "ray_sub", "ray_mul", "ray_fdiv", "ray_div", "ray_mod", "ray_xbar",
                                    "ray_left_join", "ray_inner_join", "ray_update", "ray_take", "ray_in", "ray_within", "ray_not", "ray_med",
                                    "ray_iasc", "ray_idesc", "ray_asc", "ray_desc", "ray_rank", "ray_xasc", "ray_xdesc",
-                                   "ray_asof_join", "ray_bin", "ray_binr"}; /* (in / within / not: recognised inside where: only) */
+                                   "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last"}; /* (in / within / not: recognised inside where: only; last: inside a window join's aggregates only) */
 /* xbar is recognised inside `by:` only; the standalone object model still needs a distinct function object for it:
  * this stub is never called by this library. */
 static obj_p x_stub_xbar(obj_p a, obj_p b) { (void)a; (void)b; return NULL; }
+/* ... and so does last, recognised as (last column) among a window join's aggregates only */
+static obj_p x_stub_last(obj_p a) { (void)a; return NULL; }
 static void *OUR_FN[F_N];
 static void *g_host_where, *g_host_at, *g_host_group; /* the host's built-ins behind rfx_where / rfx_at / rfx_group (NULL without a host) */
 static char g_err[640];
@@ -81,6 +85,7 @@ int rfx_host_bind(void) {
     OUR_FN[F_IASC] = (void *)rfx_iasc; OUR_FN[F_IDESC] = (void *)rfx_idesc; OUR_FN[F_ASC] = (void *)rfx_asc; OUR_FN[F_DESC] = (void *)rfx_desc;
     OUR_FN[F_RANK] = (void *)rfx_rank; OUR_FN[F_XASC] = (void *)rfx_xasc; OUR_FN[F_XDESC] = (void *)rfx_xdesc;
     OUR_FN[F_AJ] = (void *)rfx_asof_join; OUR_FN[F_BIN] = (void *)rfx_bin; OUR_FN[F_BINR] = (void *)rfx_binr;
+    OUR_FN[F_WJ] = (void *)rfx_window_join; OUR_FN[F_WJ1] = (void *)rfx_window_join1; OUR_FN[F_LAST] = (void *)x_stub_last;
     void *v = dlsym(RTLD_DEFAULT, "vector"), *t = dlsym(RTLD_DEFAULT, "table"), *e = dlsym(RTLD_DEFAULT, "eval");
     void *rs = dlsym(RTLD_DEFAULT, "ray_select"), *nu = dlsym(RTLD_DEFAULT, "__NULL_OBJ");
     if (v && t && e && rs && nu && !getenv("RFX_FORCE_STANDALONE")) {
@@ -133,7 +138,8 @@ obj_p rfx_host_fn(const char *name) {
         {"iasc", F_IASC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"idesc", F_IDESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"asc", F_ASC, RFX_TYPE_UNARY, RFX_FN_NONE},
         {"desc", F_DESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"rank", F_RANK, RFX_TYPE_UNARY, RFX_FN_NONE}, {"xasc", F_XASC, RFX_TYPE_BINARY, RFX_FN_NONE},
         {"xdesc", F_XDESC, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"asof-join", F_AJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"bin", F_BIN, RFX_TYPE_BINARY, RFX_FN_NONE}, {"binr", F_BINR, RFX_TYPE_BINARY, RFX_FN_NONE}};
+        {"asof-join", F_AJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"bin", F_BIN, RFX_TYPE_BINARY, RFX_FN_NONE}, {"binr", F_BINR, RFX_TYPE_BINARY, RFX_FN_NONE},
+        {"window-join", F_WJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"window-join1", F_WJ1, RFX_TYPE_VARY, RFX_FN_NONE}, {"last", F_LAST, RFX_TYPE_UNARY, RFX_FN_AGGR}};
     rfx_host_bind();
     for (size_t i = 0; i < sizeof(T) / sizeof(T[0]); i++)
         if (strcmp(T[i].n, name) == 0) {
@@ -188,3 +194,4 @@ static int fn_id(obj_p o) {
 #include "rfx_ops_verbs.c"
 #include "rfx_ops_sort.c"
 #include "rfx_ops_asof.c"
+#include "rfx_ops_window.c"

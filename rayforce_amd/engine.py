@@ -452,6 +452,12 @@ class Engine:
         from . import joins
         return joins.asof_join(self, keys, left, right)
 
+    def window_join(self, keys, windows, left, right, aggs, closed: bool = False) -> Dict[str, torch.Tensor]:
+        """``(window-join keys windows left right aggs)`` (``closed``: window-join1): the last of ``keys`` is the window column, ``windows``
+        the pair (lower, upper) of bounds per left row, ``aggs`` maps a result name to (aggregate, right column)."""
+        from . import joins
+        return joins.window_join(self, keys, windows, left, right, aggs, closed)
+
     def bin(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """``(bin x y)``: per cell of y the last probe position of the reference's binary search with x[mid] <= y, else -1."""
         from . import joins

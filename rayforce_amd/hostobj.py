@@ -46,6 +46,9 @@ OPS_PROTOTYPES = {
     "rfx_bin": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_binr": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_last_asof_on_gpu": (C.c_int, []),
+    "rfx_window_join": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
+    "rfx_window_join1": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
+    "rfx_last_window_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),

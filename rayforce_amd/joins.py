@@ -134,3 +134,64 @@ def bin_search(eng, x: torch.Tensor, y: torch.Tensor, right: bool) -> torch.Tens
     eng._xcheck(eng.lib.rfx_exec_bin(eng._x, x.data_ptr(), x.numel(), y.data_ptr(), y.numel(), int(bool(right)), out.data_ptr()), "bin")
     eng.sync()
     return out
+
+
+def window_ranges(eng, keys, time, windows, left: Dict[str, torch.Tensor], right: Dict[str, torch.Tensor], closed: bool = False):
+    """The window join's build and probe (rfx_exec_window_ranges): (perm, li, ri, long_windows, longest) -- the right rows in the stable order of
+    (key tuple, ``time``), and per left row the first and last position of its window in that order, (-1, -2) for the null row.  i64 columns
+    throughout; the times and the bounds hold 32-bit values (the reference compares them as such)."""
+    keys = [keys] if isinstance(keys, str) else list(keys)
+    if not keys:
+        raise RfxError("window_join needs at least one equality key")
+    lk = [eng._check_col(eng._resolve(k, left)) for k in keys]
+    rk = [eng._check_col(eng._resolve(k, right)) for k in keys]
+    nl, nr = lk[0].numel(), rk[0].numel()
+    rt = eng._check_col(eng._resolve(time, right), nr)
+    lo, hi = (eng._check_col(w, nl) for w in windows)
+    if any(c.dtype != torch.int64 for c in lk + rk + [rt, lo, hi]):
+        raise RfxError("window join keys, times and bounds must be i64-like columns on this path")
+    perm, li, ri = eng.empty(nr), eng.empty(nl), eng.empty(nl)
+    k = len(keys)
+    col, stats = C.c_int(0), (C.c_int64 * 2)()
+    rc = eng.lib.rfx_exec_window_ranges(eng._x, (C.c_void_p * k)(*[c.data_ptr() for c in lk]), (C.c_void_p * k)(*[c.data_ptr() for c in rk]), k, lo.data_ptr(),
+                                         hi.data_ptr(), rt.data_ptr(), nl, nr, int(bool(closed)), perm.data_ptr(), li.data_ptr(), ri.data_ptr(), stats, C.byref(col))
+    if rc != L.RFX_OK and col.value:
+        raise RfxError("window join: two key tuples share one 64-bit row hash (collision); not answered on this path")
+    eng._xcheck(rc, "window_ranges")
+    return perm, li, ri, int(stats[0]), int(stats[1])
+
+def window_fold(eng, vals: torch.Tensor, perm, li: torch.Tensor, ri: torch.Tensor, long_windows: int, aggs) -> Dict[str, torch.Tensor]:
+    """Every aggregate of ``aggs`` (names of RFX_WAGG) of ONE right column over the windows, in one launch (rfx_exec_window_fold); ``perm`` None:
+    ``vals`` is in the sorted order already."""
+    eng._check_col(vals)
+    if vals.dtype not in (torch.int64, torch.float64):
+        raise RfxError("window join aggregates take I64 or F64 columns on this path")
+    nl = li.numel()
+    outs, ptrs = {}, (C.c_void_p * len(L.RFX_WAGG))()
+    for a in aggs:
+        if a not in L.RFX_WAGG:
+            raise RfxError(f"window join: {a} is not one of {', '.join(L.RFX_WAGG)}")
+        dt = torch.int64 if a == "count" else torch.float64 if a == "avg" else vals.dtype
+        outs[a] = torch.empty(nl, dtype=dt, device=eng.device)
+        ptrs[L.RFX_WAGG[a]] = outs[a].data_ptr()
+    eng._xcheck(eng.lib.rfx_exec_window_fold(eng._x, vals.data_ptr(), L.RFX_F64 if vals.dtype == torch.float64 else L.RFX_I64, perm.data_ptr() if perm is not None else None,
+                                             li.data_ptr(), ri.data_ptr(), nl, vals.numel(), long_windows, ptrs), "window_fold")
+    return outs
+
+def window_join(eng, keys, windows, left: Dict[str, torch.Tensor], right: Dict[str, torch.Tensor], aggs, closed: bool = False) -> Dict[str, torch.Tensor]:
+    """``(window-join [k1 .. kn t] windows left right {name: (agg col) ...})`` -- ray_window_join / ray_window_join1 (``closed``), core/join.c:358-489:
+    the left table's columns, then one column per entry of ``aggs`` = {name: (agg, right column)}."""
+    keys = list(keys)
+    if len(keys) < 2:
+        raise RfxError("window_join needs at least one equality key and the window column")
+    perm, li, ri, nlong, _ = window_ranges(eng, keys[:-1], keys[-1], windows, left, right, closed)
+    out = dict(left)
+    by_col: Dict[str, list] = {}
+    for name, (agg, col) in aggs.items():
+        if col not in right:
+            raise RfxError(f"window join: the right table has no column {col}")
+        by_col.setdefault(col, []).append(agg)
+    folded = {col: window_fold(eng, right[col], perm, li, ri, nlong, sorted(set(a))) for col, a in by_col.items()}
+    for name, (agg, col) in aggs.items():
+        out[name] = folded[col][agg]
+    return out
