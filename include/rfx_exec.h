@@ -242,6 +242,31 @@ int rfx_exec_window_ranges(rfx_exec_t *x, const void *const *d_left_keys, const 
 int rfx_exec_window_fold(rfx_exec_t *x, const void *d_vals, int32_t type, const int64_t *d_perm, const int64_t *d_li, const int64_t *d_ri, int64_t nleft,
                          int64_t nright, int64_t long_windows, void *const *d_outs);
 
+/* ---- set verbs (rfx_set.hip): one shard only (RFX_ELIMIT "distinct over a sharded column", ...) ----
+ * Keys are 8-byte integer cells (I64 / SYMBOL / TIMESTAMP) compared as raw integers, null equal to null.  Every call takes the REFERENCE's route,
+ * decided from the key scopes as it decides (MAX_RANGE = 2^20, core/index.c:36), and reports it in *route (may be NULL).
+ * rfx_exec_distinct (index_distinct_i64, core/index.c:551-607): the distinct cells of d_a[0 .. na) followed by d_b[0 .. nb) (nb = 0: `distinct`;
+ *   else `union`, the concatenation is never made) into d_out (na + nb cells of room), *nout of them.  range = max - min + 1 over EVERY cell:
+ *   DENSE when range <= len or range <= 2^20 -- the values ascending; else HASH -- the keys in the slot order of the reference's linear-probing
+ *   table of rfx_set_table_cells(len) cells filled in row order (nulls skipped), rebuilt by a parallel priority insert.
+ * rfx_exec_member: want_first = 0, `in x y` (index_in_i64_i64, :1291-1361): d_out = nx B8 bytes (8-byte aligned), cell i = x[i] occurs in y;
+ *   want_first = 1, `find x y` (index_find_i64, :1507-1574): d_out = ny I64 cells, cell j = the first row of x holding y[j], or null -- and NOTHING
+ *   is written when nx = 0 (the reference answers I64(0) then).  DISJOINT: the two scopes do not meet (nobody is found, no table); DENSE: the
+ *   intersection spans at most 2^20 -- a bitmap / a first-row table over it; else HASH.
+ * rfx_exec_set_filter: the cells of x that occur (keep_members = 1: `sect`) / do not occur (0: `except`) in y, in x's order, into d_out (nx cells
+ *   of room, not x itself), *nout of them: filter(x, in(x, y)) as ONE probe + ordered compaction of the values.  y_is_atom: y is the one cell `atom`.
+ * RFX_ESTATE with *route = RFX_SET_ROUTE_UNDEFINED: the reference's own indexing would leave its table for these cells -- a hash route over a
+ *   negative key (its probes start at (i64)key % size), for `find` over a null too, or a range that does not fit 64 bits: nothing is answered, the
+ *   reason is in rfx_exec_last_error().  Scratch (hash routes: 16-24 B per set cell x 2..4) comes from the context's pool and is freed before return.
+ * RFX_XSTAT_SET_DISTINCTS / _MEMBERS / _FILTERS count what ran, RFX_XSTAT_NS_SET_BUILD / _PROBE the two halves' wall time. */
+enum { RFX_SET_ROUTE_UNDEFINED = -1, RFX_SET_ROUTE_NONE = 0, RFX_SET_ROUTE_DENSE = 1, RFX_SET_ROUTE_HASH = 2, RFX_SET_ROUTE_DISJOINT = 3, RFX_SET_ROUTE_ATOM = 4 };
+int rfx_exec_distinct(rfx_exec_t *x, const int64_t *d_a, int64_t na, const int64_t *d_b, int64_t nb, int64_t *d_out, int64_t *nout, int *route);
+int rfx_exec_member(rfx_exec_t *x, const int64_t *d_x, int64_t nx, const int64_t *d_y, int64_t ny, int want_first, void *d_out, int *route);
+int rfx_exec_set_filter(rfx_exec_t *x, const int64_t *d_x, int64_t nx, const int64_t *d_y, int64_t ny, int y_is_atom, int64_t atom, int keep_members,
+                        int64_t *d_out, int64_t *nout, int *route);
+/* cells of the reference's table for `len` rows: the first prime >= ceil(len / 0.75) (ht_oa_create, core/hash.c:35-56; host only) */
+int64_t rfx_set_table_cells(int64_t len);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -273,7 +298,12 @@ enum {
     RFX_XSTAT_SEARCHES = 20,     /* ... binary searches those two ran (left rows of an asof join with a right side, cells of a bin / binr) */
     RFX_XSTAT_NS_ASOF_BUILD = 21, /* wall time of the asof joins' build halves (right side only), nanoseconds, to the stream idle */
     RFX_XSTAT_NS_ASOF_PROBE = 22, /* ... and of their probe halves */
-    RFX_XSTAT_N = 23
+    RFX_XSTAT_SET_DISTINCTS = 23, /* distinct / union calls answered by the device path */
+    RFX_XSTAT_SET_MEMBERS = 24,   /* in / find calls */
+    RFX_XSTAT_SET_FILTERS = 25,   /* sect / except calls */
+    RFX_XSTAT_NS_SET_BUILD = 26,  /* wall time of the set verbs' scope + build halves, nanoseconds, to the stream idle */
+    RFX_XSTAT_NS_SET_PROBE = 27,  /* ... and of their probe / emit halves */
+    RFX_XSTAT_N = 28
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

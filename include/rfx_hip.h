@@ -695,6 +695,48 @@ int rfx_hip_window_ranges(rfx_ctx_t *ctx, const int64_t *d_lo, const int64_t *d_
 int rfx_hip_window_fold(rfx_ctx_t *ctx, const void *d_vals, int32_t type, int64_t nvals, const int64_t *d_li, const int64_t *d_ri, int64_t n,
                         int64_t long_windows, void *const *d_outs);
 
+/* ---- set verbs (rfx_set.hip): distinct / find / in / sect / except / union over 8-byte keys (core/index.c:551-607,1291-1361,1507-1574) ----
+ * Every key column is given as TWO spans (d_a[0 .. na), d_b[0 .. nb); nb = 0: one column): `union` is `distinct` of a concatenation that is
+ * never materialised, rows of b count from na.
+ * rfx_hip_set_scope: out[0] = min, out[1] = max over every cell (nulls included, as index_scope_i64), out[2] = min over the non-null cells
+ *   (INT64_MAX when there is none), out[3] = number of null cells.  na + nb > 0.  (syncs)
+ * rfx_hip_set_mark: bit (v - kmin) of d_bits (zeroed by the caller, (range + 63) / 64 words) is set for every cell v inside
+ *   [kmin, kmin + range); cells outside are ignored (the `in` set is marked over the intersection of two scopes only).
+ * rfx_hip_set_first_dense: d_first[v - kmin] = the first row holding v (cells pre-filled with INT64_MAX = nobody), cells outside ignored.
+ * rfx_hip_set_hash_build: an open-addressed table of `capacity` (a power of two, >= 2 x the non-null cells) slots: d_keys (pre-filled with
+ *   NULL_I64 = empty) and, unless NULL, d_first (pre-filled with INT64_MAX) = the first row of the slot's key.  Null cells are skipped.
+ * rfx_hip_set_probe: what every cell of d_q finds in a lookup structure, written by out_mode:
+ *   RFX_SET_OUT_B8 one byte 0 / 1 per cell (d_out 8-byte aligned); RFX_SET_OUT_FIRST an i64 per cell, the first row or NULL_I64;
+ *   RFX_SET_OUT_FLAGS / _NOT_FLAGS one BIT per cell ((n + 63) / 64 words, whole words written): member / not member.
+ * rfx_hip_set_priority_insert: the reference's linear-probing table of P cells (ht_oa_create, core/hash.c:36-56) rebuilt in parallel: every
+ *   occupied slot of the hashed table puts its first row into d_cells (pre-filled with INT64_MAX) from cell key % P on by atomic MIN, carrying
+ *   the displaced larger row on, wrapping at P.  Keys must be non-negative; distinct keys < P.  rfx_hip_set_cells_flags: bit i = cell i occupied.
+ * rfx_hip_set_compact: ordered compaction of the set bits of d_flags[0 .. nbits), ascending: RFX_SET_EMIT_OFFSET writes kmin + i,
+ *   RFX_SET_EMIT_SRC writes d_src[i], RFX_SET_EMIT_ROWKEY writes the key at row d_src[i] of the two spans.  d_scan: nbits / 16384 + 2 cells of
+ *   scratch.  At most cap cells are written; *count = the number of set bits (RFX_ELIMIT, nothing written, when it exceeds cap).  (syncs) */
+enum { RFX_SET_BITS = 0, RFX_SET_DENSE_FIRST = 1, RFX_SET_HASH = 2, RFX_SET_ATOM = 3 };
+enum { RFX_SET_OUT_B8 = 0, RFX_SET_OUT_FIRST = 1, RFX_SET_OUT_FLAGS = 2, RFX_SET_OUT_NOT_FLAGS = 3 };
+enum { RFX_SET_EMIT_OFFSET = 0, RFX_SET_EMIT_SRC = 1, RFX_SET_EMIT_ROWKEY = 2 };
+typedef struct rfx_set_lookup {
+    int32_t kind;      /* RFX_SET_BITS (d_bits over [kmin, kmin + range)), _DENSE_FIRST (d_first over the same), _HASH (d_keys / d_first), _ATOM */
+    int32_t null_hit;  /* _HASH: what a null cell of d_q finds (the table holds no null): 1 = member */
+    int64_t kmin, range;
+    const uint64_t *d_bits;
+    const int64_t *d_first; /* _DENSE_FIRST: range cells; _HASH: capacity cells or NULL */
+    const int64_t *d_keys;  /* _HASH: capacity cells */
+    int64_t capacity;
+    int64_t atom;           /* _ATOM: the one member */
+} rfx_set_lookup_t;
+int rfx_hip_set_scope(rfx_ctx_t *ctx, const int64_t *d_a, int64_t na, const int64_t *d_b, int64_t nb, int64_t *out4);
+int rfx_hip_set_mark(rfx_ctx_t *ctx, const int64_t *d_a, int64_t na, const int64_t *d_b, int64_t nb, int64_t kmin, int64_t range, uint64_t *d_bits);
+int rfx_hip_set_first_dense(rfx_ctx_t *ctx, const int64_t *d_x, int64_t nx, int64_t kmin, int64_t range, int64_t *d_first);
+int rfx_hip_set_hash_build(rfx_ctx_t *ctx, const int64_t *d_a, int64_t na, const int64_t *d_b, int64_t nb, int64_t *d_keys, int64_t *d_first, int64_t capacity);
+int rfx_hip_set_probe(rfx_ctx_t *ctx, const rfx_set_lookup_t *s, const int64_t *d_q, int64_t n, int out_mode, void *d_out);
+int rfx_hip_set_priority_insert(rfx_ctx_t *ctx, const int64_t *d_keys, const int64_t *d_first, int64_t capacity, int64_t P, int64_t *d_cells);
+int rfx_hip_set_cells_flags(rfx_ctx_t *ctx, const int64_t *d_cells, int64_t P, uint64_t *d_flags);
+int rfx_hip_set_compact(rfx_ctx_t *ctx, const uint64_t *d_flags, int64_t nbits, int mode, int64_t kmin, const int64_t *d_src, const int64_t *d_a, int64_t na,
+                        const int64_t *d_b, int64_t *d_scan, int64_t cap, int64_t *d_out, int64_t *count);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -38,6 +38,11 @@
  *   rfx_asof_join          ray_asof_join         core/join.c:300-356             vary_f    (key symbols, the last one the asof column; left table, right table)
  *   rfx_bin rfx_binr       ray_bin ray_binr      core/items.c:1399-1644          binary_f  (I64 / TIMESTAMP vector, vector of the same type) -> I64 positions
  *   rfx_window_join rfx_window_join1  ray_window_join ray_window_join1  core/join.c:358-489  vary_f  (key symbols, windows, left table, right table, aggregates)
+ *   rfx_distinct           ray_distinct          core/compose.c:839              unary_f   I64 / SYMBOL / TIMESTAMP vector -> its distinct cells, ATTR_DISTINCT
+ *   rfx_in                 ray_in                core/items.c:736                binary_f  (x, y) two such vectors of one type -> B8, x[i] occurs in y
+ *   rfx_find               ray_find              core/items.c:302                binary_f  (x, y) -> I64, the first row of x holding y[j], or null
+ *   rfx_sect rfx_except    ray_sect ray_except   core/items.c:898-1019           binary_f  (x, y) I64 or SYMBOL pairs -> the cells of x in / not in y, in x's order
+ *   rfx_union              ray_union             core/items.c:1022               binary_f  (x, y) -> distinct of x followed by y, ATTR_DISTINCT
  *
  * Everything below runs on the MI355X through the flat ABI of rfx_hip.h.  There is NO CPU implementation behind these
  * entry points: queries whose shape the GPU path does not cover are handed back to the host's own ray_* function when
@@ -174,6 +179,30 @@ rfx_obj_p rfx_window_join(rfx_obj_p *x, int64_t n);
 rfx_obj_p rfx_window_join1(rfx_obj_p *x, int64_t n);
 /* 1: the last of those two calls ran on the device; 0: its left table was empty, or it went to the host */
 int rfx_last_window_on_gpu(void);
+
+/* The set verbs over plain I64 / SYMBOL / TIMESTAMP vectors (host vectors or device-column handles) on the device (rfx_set.hip), each on the ROUTE the
+ * reference takes for the same cells (index_distinct_i64, index_in_i64_i64, index_find_i64: core/index.c:551-607,1291-1361,1507-1574):
+ *   distinct / union: dense (max - min + 1 <= len or <= 2^20) the values ascending, else the keys in the slot order of the reference's linear-probing
+ *     table -- the result carries x's type and ATTR_DISTINCT; in -> B8 of x's length; find -> I64 of y's length (I64(0) when x is empty);
+ *     sect / except (I64 or SYMBOL pairs; except also a vector and an atom of its type) -> the kept cells of x, x's type, no attribute.
+ * The host's own verb answers every other shape -- atoms elsewhere, ENUM / MAPLIST / parted / 1-2-4-byte / F64 / GUID / LIST operands, two types,
+ * tables, sharded columns, scratch that does not fit -- every error the reference words itself, and every shape for which the reference's tables are
+ * indexed outside themselves (a hash route over a negative key, `find`'s over a null, a range beyond 64 bits: DESIGN.md section 4); without a host
+ * those are refused ("not covered ... no host function").  The reason is in rfx_ops_last_error(). */
+rfx_obj_p rfx_distinct(rfx_obj_p x);
+rfx_obj_p rfx_find(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_in(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_sect(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_except(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_union(rfx_obj_p x, rfx_obj_p y);
+/* 1: the last of those six calls was answered by the device path (an empty operand included: no launch); 0: it went to the host or failed.
+ * rfx_last_set_route: the route it took, RFX_SET_ROUTE_* of rfx_exec.h (1 dense, 2 hash, 3 disjoint scopes, 4 except's atom, 0 nothing to do) */
+int rfx_last_set_on_gpu(void);
+int rfx_last_set_route(void);
+/* unary_f: I64[7] counters of those six verbs since load: {calls answered by the device path, calls handed to the host (or refused for want of one),
+ * then the answered calls by route: nothing to look up, dense, hash, disjoint scopes, except's atom}; the argument is ignored.  Loadable like
+ * rfx_stats, whose 17 cells stay what they were: what tells a host that the device answered. */
+rfx_obj_p rfx_set_stats(rfx_obj_p ignored);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

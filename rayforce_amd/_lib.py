@@ -106,6 +106,11 @@ class HashTables(C.Structure):
                 ("d_first", C.c_void_p), ("d_acc", C.c_void_p * RFX_MAX_AGGS), ("d_cnt", C.c_void_p * RFX_MAX_AGGS)]
 
 
+class SetLookup(C.Structure):  # rfx_set_lookup_t
+    _fields_ = [("kind", C.c_int32), ("null_hit", C.c_int32), ("kmin", C.c_int64), ("range", C.c_int64), ("d_bits", C.c_void_p), ("d_first", C.c_void_p),
+                ("d_keys", C.c_void_p), ("capacity", C.c_int64), ("atom", C.c_int64)]
+
+
 assert C.sizeof(Pred) == 40 and C.sizeof(Agg) == 56 and C.sizeof(XNode) == 56 and C.sizeof(Partial) == 64 and C.sizeof(Value) == 16
 
 # ---- include/rfx_exec.h: the planner's structures ----
@@ -119,6 +124,8 @@ RFX_XSTAT_SCOPE_SAMPLED, RFX_XSTAT_SCOPE_RETRIED, RFX_XSTAT_SCOPE_REMEMBERED, RF
     RFX_XSTAT_NS_EMIT, RFX_XSTAT_NS_FETCH, RFX_XSTAT_NS_TOTAL = range(16)
 RFX_XSTAT_SORTS, RFX_XSTAT_SORT_PASSES = 16, 17
 RFX_XSTAT_ASOF_JOINS, RFX_XSTAT_BINS, RFX_XSTAT_SEARCHES, RFX_XSTAT_NS_ASOF_BUILD, RFX_XSTAT_NS_ASOF_PROBE = 18, 19, 20, 21, 22
+RFX_XSTAT_SET_DISTINCTS, RFX_XSTAT_SET_MEMBERS, RFX_XSTAT_SET_FILTERS, RFX_XSTAT_NS_SET_BUILD, RFX_XSTAT_NS_SET_PROBE = 23, 24, 25, 26, 27
+RFX_SET_ROUTE_UNDEFINED, RFX_SET_ROUTE_NONE, RFX_SET_ROUTE_DENSE, RFX_SET_ROUTE_HASH, RFX_SET_ROUTE_DISJOINT, RFX_SET_ROUTE_ATOM = -1, 0, 1, 2, 3, 4
 RFX_WAGG = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "first": 5, "last": 6}  # include/rfx_hip.h RFX_WAGG_*
 RFX_XSTAT_PHASES = (("scope", 9), ("pass", 10), ("merge", 11), ("rank", 12), ("emit", 13), ("fetch", 14), ("total", 15))
 
@@ -278,6 +285,15 @@ PROTOTYPES = {
     "rfx_hip_inverse_perm": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_set_scope": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    "rfx_hip_set_mark": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_set_first_dense": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_set_hash_build": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "rfx_hip_set_probe": (C.c_int, [_ctx, _P(SetLookup), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "rfx_hip_set_priority_insert": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_set_cells_flags": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_set_compact": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                            _P(C.c_int64)]),
     "rfx_hip_window_ranges": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rfx_hip_window_fold": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _P(C.c_void_p)]),
     "rfx_hip_eval_expr": (C.c_int, [_ctx, _P(Agg), C.c_int64, C.c_void_p, _P(C.c_int32)]),
@@ -345,6 +361,10 @@ EXEC_PROTOTYPES = {
     "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
                                C.c_void_p, C.c_void_p, _P(C.c_int64), _P(C.c_int)]),
     "rfx_exec_window_fold": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _P(C.c_void_p)]),
+    "rfx_exec_distinct": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, _P(C.c_int64), _P(C.c_int)]),
+    "rfx_exec_member": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, _P(C.c_int)]),
+    "rfx_exec_set_filter": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, _P(C.c_int64), _P(C.c_int)]),
+    "rfx_set_table_cells": (C.c_int64, [C.c_int64]),
     "rfx_exec_join_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_join_index_shard": (C.c_int, [_exec, C.c_int, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_stat": (C.c_int64, [_exec, C.c_int]),

@@ -49,16 +49,18 @@ static struct {
     const char *(*symname)(int64_t);
     obj_p null_obj;
     /* the host's own built-ins, for recognising function objects inside parsed expressions and for delegation */
-    void *f[48];
+    void *f[64];
 } H;
 /* F_SUM .. F_FIRST are the aggregates rfx_select / rfx_update map (they test that id RANGE); the ids after F_BINR are not: F_LAST is recognised by
- * window_agg (rfx_ops_window.c) alone, and every other reader of fn_id must keep refusing it */
-enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_N };
+ * window_agg (rfx_ops_window.c) alone, and every other reader of fn_id must keep refusing it; F_DISTINCT .. F_UNION (and F_IN as a verb of its own) are the
+ * set verbs of rfx_ops_set.c: no reader of fn_id maps them -- inside where: F_IN stays the comparison list of rfx_ops_plan.c and nothing else */
+enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_N };
 static const char *HOST_FN[F_N] = {"ray_sum", "ray_avg", "ray_min", "ray_max", "ray_count", "ray_first", "ray_eq",  "ray_ne",  "ray_lt",  "ray_gt",
                                    "ray_le",  "ray_ge",  "ray_and", "ray_or",  "ray_select", "ray_add",  "ray_sub", "ray_mul", "ray_fdiv", "ray_div", "ray_mod", "ray_xbar",
                                    "ray_left_join", "ray_inner_join", "ray_update", "ray_take", "ray_in", "ray_within", "ray_not", "ray_med",
                                    "ray_iasc", "ray_idesc", "ray_asc", "ray_desc", "ray_rank", "ray_xasc", "ray_xdesc",
-                                   "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last"}; /* (in / within / not: recognised inside where: only; last: inside a window join's aggregates only) */
+                                   "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last",
+                                   "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union"}; /* (in / within / not: recognised inside where: only; last: inside a window join's aggregates only) */
 /* xbar is recognised inside `by:` only; the standalone object model still needs a distinct function object for it:
  * this stub is never called by this library. */
 static obj_p x_stub_xbar(obj_p a, obj_p b) { (void)a; (void)b; return NULL; }
@@ -86,6 +88,8 @@ int rfx_host_bind(void) {
     OUR_FN[F_RANK] = (void *)rfx_rank; OUR_FN[F_XASC] = (void *)rfx_xasc; OUR_FN[F_XDESC] = (void *)rfx_xdesc;
     OUR_FN[F_AJ] = (void *)rfx_asof_join; OUR_FN[F_BIN] = (void *)rfx_bin; OUR_FN[F_BINR] = (void *)rfx_binr;
     OUR_FN[F_WJ] = (void *)rfx_window_join; OUR_FN[F_WJ1] = (void *)rfx_window_join1; OUR_FN[F_LAST] = (void *)x_stub_last;
+    OUR_FN[F_IN] = (void *)rfx_in; OUR_FN[F_DISTINCT] = (void *)rfx_distinct; OUR_FN[F_FIND] = (void *)rfx_find; OUR_FN[F_SECT] = (void *)rfx_sect;
+    OUR_FN[F_EXCEPT] = (void *)rfx_except; OUR_FN[F_UNION] = (void *)rfx_union;
     void *v = dlsym(RTLD_DEFAULT, "vector"), *t = dlsym(RTLD_DEFAULT, "table"), *e = dlsym(RTLD_DEFAULT, "eval");
     void *rs = dlsym(RTLD_DEFAULT, "ray_select"), *nu = dlsym(RTLD_DEFAULT, "__NULL_OBJ");
     if (v && t && e && rs && nu && !getenv("RFX_FORCE_STANDALONE")) {
@@ -139,7 +143,9 @@ obj_p rfx_host_fn(const char *name) {
         {"desc", F_DESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"rank", F_RANK, RFX_TYPE_UNARY, RFX_FN_NONE}, {"xasc", F_XASC, RFX_TYPE_BINARY, RFX_FN_NONE},
         {"xdesc", F_XDESC, RFX_TYPE_BINARY, RFX_FN_NONE},
         {"asof-join", F_AJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"bin", F_BIN, RFX_TYPE_BINARY, RFX_FN_NONE}, {"binr", F_BINR, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"window-join", F_WJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"window-join1", F_WJ1, RFX_TYPE_VARY, RFX_FN_NONE}, {"last", F_LAST, RFX_TYPE_UNARY, RFX_FN_AGGR}};
+        {"window-join", F_WJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"window-join1", F_WJ1, RFX_TYPE_VARY, RFX_FN_NONE}, {"last", F_LAST, RFX_TYPE_UNARY, RFX_FN_AGGR},
+        {"distinct", F_DISTINCT, RFX_TYPE_UNARY, RFX_FN_NONE}, {"find", F_FIND, RFX_TYPE_BINARY, RFX_FN_NONE}, {"in", F_IN, RFX_TYPE_BINARY, RFX_FN_NONE},
+        {"sect", F_SECT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"except", F_EXCEPT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"union", F_UNION, RFX_TYPE_BINARY, RFX_FN_NONE}};
     rfx_host_bind();
     for (size_t i = 0; i < sizeof(T) / sizeof(T[0]); i++)
         if (strcmp(T[i].n, name) == 0) {
@@ -195,3 +201,4 @@ static int fn_id(obj_p o) {
 #include "rfx_ops_sort.c"
 #include "rfx_ops_asof.c"
 #include "rfx_ops_window.c"
+#include "rfx_ops_set.c"

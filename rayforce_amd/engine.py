@@ -73,6 +73,7 @@ class Engine:
         self._x = C.c_void_p()
         L.check(self.lib.rfx_exec_create(self._ctxs, self.shards, C.byref(self._x)), "exec_create")
         self._keep: List = []
+        self.last_set_route = "none"  # the route of the last set verb (rayforce_amd/sets.py): none / dense / hash / disjoint / atom / undefined
 
     def close(self) -> None:
         if self._x:
@@ -467,6 +468,37 @@ class Engine:
         """``(binr x y)``: the first probe position with x[mid] >= y, else len x."""
         from . import joins
         return joins.bin_search(self, x, y, True)
+
+    # ------------------------------------------------------------------ the set verbs (rfx_set.hip): rayforce_amd/sets.py
+    def distinct(self, x: torch.Tensor) -> torch.Tensor:
+        """``(distinct x)``: ascending on the reference's dense route, in its table's slot order on the hash route (``last_set_route``)."""
+        from . import sets
+        return sets.distinct(self, x)
+
+    def union(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``(union x y)``: distinct of x followed by y; the concatenation is never made."""
+        from . import sets
+        return sets.distinct(self, x, y)
+
+    def isin(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``(in x y)``: int8 0 / 1 per cell of x."""
+        from . import sets
+        return sets.member(self, x, y, False)
+
+    def find(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``(find x y)``: per cell of y the first row of x holding it, or null; empty when x is empty."""
+        from . import sets
+        return sets.member(self, x, y, True)
+
+    def sect(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``(sect x y)``: the cells of x that occur in y, in x's order."""
+        from . import sets
+        return sets.set_filter(self, x, y, True)
+
+    def except_(self, x: torch.Tensor, y) -> torch.Tensor:
+        """``(except x y)``: the cells of x that do not occur in y (a column, or one int)."""
+        from . import sets
+        return sets.set_filter(self, x, y, False)
 
     # ------------------------------------------------------------------ the select surface (core/query.c:607-654)
     def select(self, query: Dict) -> Dict[str, torch.Tensor]:

@@ -49,6 +49,11 @@ OPS_PROTOTYPES = {
     "rfx_window_join": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
     "rfx_window_join1": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
     "rfx_last_window_on_gpu": (C.c_int, []),
+    "rfx_distinct": (C.c_void_p, [C.c_void_p]),
+    **{f"rfx_{n}": (C.c_void_p, [C.c_void_p, C.c_void_p]) for n in ("find", "in", "sect", "except", "union")},
+    "rfx_last_set_on_gpu": (C.c_int, []),
+    "rfx_last_set_route": (C.c_int, []),
+    "rfx_set_stats": (C.c_void_p, [C.c_void_p]),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),
