@@ -186,6 +186,20 @@ void rfx_exec_groups_free(rfx_exec_t *x, rfx_groups_t *g);
 int rfx_exec_median(rfx_exec_t *x, const rfx_query_t *q, const void *d_col, int32_t col_type, rfx_value_t *out);
 int rfx_exec_group_median(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_t *g, const void *d_col, int32_t col_type, void *d_out);
 
+/* ---- last, dev (rfx_lastdev.hip) ----
+ * RFX_AGG_LAST in rfx_exec_filter_aggr: the cell at the last selected row, null or not (shard order = row order; one process).  In rfx_exec_group_by:
+ * per group the cell at the highest selected row whose cell is non-null, null without one -- the reference's answer with one chunk (aggr_last,
+ * core/aggr.c:851-930) -- planned as an i64 MAX over derived rows (8 B of scratch per row and distinct LAST column), under every
+ * by: shape, over the shards of ONE device, in one process (RFX_ELIMIT otherwise); the result is whole on shard 0 (RFX_Q_SLICED is ignored, as with FIRST).
+ * rfx_exec_dev: ray_dev's rule (core/math.c:2628-2699) over the query's selection (its preds, or its d_mask) of an i64 / timestamp (RFX_I64) or f64
+ * column: l = non-null count, 0 -> null, 1 -> 0.0; favg = (f64)(wrapping i64 sum) / l resp. f64 sum / l; sqrt(sum (x - favg)^2 / l): two passes.
+ * rfx_exec_group_dev: g->groups f64 cells into d_out (on shard 0) by aggr_dev's rule (core/aggr.c:2250-2350,2864-2929): per group sum (f64)x, sum
+ * (f64)x * (f64)x and the non-null count n; 0 -> null, 1 -> 0.0, else mean = s/n, var = sq/n - mean * mean, var < 0 ? 0 : sqrt(var) (not Welford's: it
+ * cancels where the reference's does); `g` is rfx_exec_group_by's result for the same query (any by: shape): the three sums ride through the same
+ * group-by as hidden aggregates.  Scratch 16 B per row.  Both dev calls: one shard only (RFX_ELIMIT otherwise), as med. */
+int rfx_exec_dev(rfx_exec_t *x, const rfx_query_t *q, const void *d_col, int32_t col_type, rfx_value_t *out);
+int rfx_exec_group_dev(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_t *g, const void *d_col, int32_t col_type, void *d_out);
+
 /* ---- sort (rfx_sort.hip): one shard only (RFX_ELIMIT "sort over a sharded table": a sharded merge sort is its own piece of work) ----
  * rfx_exec_sort: d_perm (n i64 cells on shard 0) = the stable lexicographic order of the rows by d_cols[0] (most significant) .. d_cols[ncols-1],
  * all ascending or all descending -- one stable radix sort per column from the last to the first, each reading its keys through the running

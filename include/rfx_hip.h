@@ -64,7 +64,10 @@ enum {
     RFX_AGG_MAX = 2,   /* ray_max                                                        */
     RFX_AGG_COUNT = 3, /* ray_count: counts every selected row, nulls included           */
     RFX_AGG_AVG = 4,   /* ray_avg: sum / count_non_null as f64                           */
-    RFX_AGG_FIRST = 5  /* ray_first / aggr_first: value at the first selected row        */
+    RFX_AGG_FIRST = 5, /* ray_first / aggr_first: value at the first selected row        */
+    RFX_AGG_LAST = 6   /* ray_last: value at the last selected row (scalar, positional: null or not); under by: the value at the group's highest
+                        * selected row whose cell is non-null (aggr_last with one chunk) -- planned by rfx_exec_group_by, the grouped rfx_hip_*
+                        * entry points refuse it */
 };
 
 #define RFX_MAX_PREDS 8
@@ -159,8 +162,8 @@ typedef struct rfx_partial {
     int64_t isum; /* SUM/AVG over i64: wrapping sum of non-null values                         */
     double fsum;  /* SUM/AVG over f64 (and AVG over i64 keeps isum): sum of non-NaN values      */
     int64_t cnt;  /* SUM/AVG/MIN/MAX: number of non-null values; COUNT: number of selected rows */
-    int64_t ext;  /* MIN/MAX: extremum (f64 as raw bits); FIRST: value bits; valid iff cnt > 0  */
-    int64_t pos;  /* FIRST: global row id of the first selected row (INT64_MAX if none)         */
+    int64_t ext;  /* MIN/MAX: extremum (f64 as raw bits); FIRST / LAST: value bits; valid iff cnt > 0 */
+    int64_t pos;  /* FIRST: global row id of the first selected row (INT64_MAX if none); LAST: of the last one (valid iff cnt > 0) */
     int64_t _rsv[3];
 } rfx_partial_t;
 
@@ -611,6 +614,21 @@ int rfx_hip_unfix_f64(rfx_ctx_t *ctx, int64_t *d_hi_io, const int64_t *d_lo, con
  * d_out[r] = null for a null input, else the largest multiple of `width` (> 0) that is <= d_col[r].  Group on the result
  * (`by: {t: (xbar ts 60000)}`). */
 int rfx_hip_xbar_i64(rfx_ctx_t *ctx, const int64_t *d_col, int64_t nrows, int64_t width, int64_t *d_out);
+
+/* ---- last under by:, dev (rfx_lastdev.hip) ----
+ * rfx_hip_last_rows: d_out[i] = d_col[i] is null ? null : row0 + i -- the i64 column whose grouped MAX is, per group, the highest selected row with a
+ * non-null cell.  rfx_hip_last_gather: d_out[g] = the column's cell at row d_rows[g], read from the piece (of npieces <= 16, all on this device) whose
+ * rows [row0[p], row0[p] + len[p]) hold it; a null row, or one no piece holds, gives the typed null (NULL_I64 / NaN).  d_out may be d_rows.
+ * rfx_hip_dev_derive: d_sq[i] = null ? NaN : (f64)x * (f64)x, d_nn[i] = null ? 0 : 1.  rfx_hip_dev_finalise: aggr_dev's last step (core/aggr.c:2864-2929)
+ * from the groups' mean, mean of squares and non-null count: 0 -> null, 1 -> 0.0, else var = meansq - mean * mean, var < 0 ? 0 : sqrt(var).
+ * rfx_hip_dev: ray_dev (core/math.c:2628-2699) of a plain column in two passes -- l = non-null count (0 -> null, 1 -> 0.0), favg = (f64)(wrapping i64
+ * sum) / l (f64: f64 sum / l), sqrt(sum (x - favg)^2 / l); block partials are folded in block order: run-to-run deterministic.  (syncs) */
+int rfx_hip_last_rows(rfx_ctx_t *ctx, const void *d_col, int32_t col_type, int64_t nrows, int64_t row0, int64_t *d_out);
+int rfx_hip_last_gather(rfx_ctx_t *ctx, const void *const *d_pieces, const int64_t *row0, const int64_t *len, int npieces, int32_t col_type,
+                        const int64_t *d_rows, int64_t groups, void *d_out);
+int rfx_hip_dev_derive(rfx_ctx_t *ctx, const void *d_col, int32_t col_type, int64_t nrows, double *d_sq, int64_t *d_nn);
+int rfx_hip_dev_finalise(rfx_ctx_t *ctx, const double *d_mean, const double *d_meansq, const int64_t *d_cnt, int64_t groups, double *d_out);
+int rfx_hip_dev(rfx_ctx_t *ctx, const void *d_col, int32_t col_type, int64_t nrows, rfx_value_t *out);
 
 /* ---- exact medians (rfx_median.hip): `med` scalar (ray_med, core/math.c:2529-2626) and grouped (aggr_med, core/aggr.c:2136-2247) ----
  * A group's median is its selected values of ranks (l-1)/2 and l/2 -- nulls included -- under the reference's sort keys (core/sort.c:266-311:

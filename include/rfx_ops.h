@@ -25,6 +25,7 @@
  *   rfx_sum rfx_avg        ray_sum ray_avg       core/math.c:2388,2445-2526      unary_f   vector | MAPFILTER(val, ids)
  *   rfx_min rfx_max        ray_min ray_max       core/math.c:2428-2429           unary_f
  *   rfx_count rfx_first    ray_count ray_first   core/misc.c:43-60, core/items.c unary_f
+ *   rfx_last rfx_dev       ray_last ray_dev      core/items.c:1112-1114, core/math.c:2628-2699   unary_f
  *   rfx_at                 at_ids via ray_at     core/rayforce.c:1100-1158       binary_f  (column, I64 ids) -> gathered column
  *   rfx_left_join          ray_left_join         core/join.c:158-198             vary_f    (key symbols, left table, right table)
  *   rfx_inner_join         ray_inner_join        core/join.c:200-298             vary_f
@@ -129,6 +130,15 @@ rfx_obj_p rfx_min(rfx_obj_p x);
 rfx_obj_p rfx_max(rfx_obj_p x);
 rfx_obj_p rfx_count(rfx_obj_p x);
 rfx_obj_p rfx_first(rfx_obj_p x);
+/* ray_last (core/items.c:1112-1114): a vector's last cell and a MAPFILTER pair's last collected cell, null or not; per group of a MAPGROUP pair (IDS / SHIFT
+ * index, with or without filter ids) the last NON-NULL cell, null without one -- aggr_last's answer with one chunk (core/aggr.c:851-930), which is also its
+ * answer whenever aggr_map does not split; with several executors and 16 384 selected rows or more the reference keeps the first chunk's value instead
+ *  */
+rfx_obj_p rfx_last(rfx_obj_p x);
+/* ray_dev (core/math.c:2628-2699): an I64 / F64 vector or a MAPFILTER over one -> the population standard deviation of the non-null cells as F64 (two
+ * passes: favg, then sqrt(sum (x - favg)^2 / l)); a MAPGROUP over I64 / TIMESTAMP / F64 values -> aggr_dev's per-group sqrt(max(0, sq/n - (s/n)^2))
+ * (core/aggr.c:2250-2350,2864-2929; rfx_lastdev.hip); every other argument is the host's ray_dev */
+rfx_obj_p rfx_dev(rfx_obj_p x);
 /* ray_med (core/math.c:2529-2626): an I64 vector, a MAPFILTER over one, or a MAPGROUP (IDS / SHIFT index, with or without filter ids) over I64 /
  * TIMESTAMP / F64 values -> the exact median(s) as F64 (rfx_median.hip); every other argument is the host's ray_med */
 rfx_obj_p rfx_med(rfx_obj_p x);
@@ -233,7 +243,9 @@ int rfx_ops_set_validation(int mode);
  * (2^e > max |x|, 2^b >= rows): absolute, so a group of values far below the column's largest loses relative precision; mode 2 (RFX_DETERMINISTIC=2): a
  * SECOND limb adds up what the first one's cells rounded away, scaled by 2^(62 - b) more -- 2^(e + 2b - 124) per cell, below an f64 sum's own rounding for
  * any data whose magnitudes span less than ~2^60; one more i64 sum per aggregate.  The images of a resident column are made once and cached with it (8 bytes
- * of HBM per row and limb); a column holding a NaN or an infinity keeps the default path.  DESIGN.md section 4. */
+ * of HBM per row and limb); a column holding a NaN or an infinity keeps the default path.  DESIGN.md section 4.
+ * The reproducible modes do not cover `dev`: rfx_dev / rfx_exec_group_dev keep their three f64 sums per group through the default path's atomics in
+ * either mode (the scalar dev folds its block partials in a fixed order and is run-to-run stable without them). */
 int rfx_ops_set_deterministic(int mode);
 /* One process per device (rfx_ops_dist_init, or a transport on the planner): 1 = a grouped rfx_select returns only THIS rank's range of the groups
  * (rfx_exec_split(groups, ranks, rank) in the answer's order: the ranks' tables end to end are the answer) instead of the whole answer on every rank; also

@@ -10,7 +10,7 @@ RFX_ESTATE = -6
 RFX_B8, RFX_I64, RFX_F64 = 1, 5, 10
 RFX_EQ, RFX_NE, RFX_LT, RFX_GT, RFX_LE, RFX_GE = range(6)
 RFX_AND, RFX_OR = 0, 1
-RFX_AGG_SUM, RFX_AGG_MIN, RFX_AGG_MAX, RFX_AGG_COUNT, RFX_AGG_AVG, RFX_AGG_FIRST = range(6)
+RFX_AGG_SUM, RFX_AGG_MIN, RFX_AGG_MAX, RFX_AGG_COUNT, RFX_AGG_AVG, RFX_AGG_FIRST, RFX_AGG_LAST = range(7)
 RFX_MAX_PREDS = RFX_MAX_AGGS = RFX_MAX_COLS = RFX_MAX_KEYS = 8
 RFX_RANK_SMALL = 2048
 RFX_MAX_EXPRS = 4
@@ -19,7 +19,7 @@ INF_I64 = 2**63 - 1
 
 OPS = {"==": RFX_EQ, "!=": RFX_NE, "<": RFX_LT, ">": RFX_GT, "<=": RFX_LE, ">=": RFX_GE}
 AGGS = {"sum": RFX_AGG_SUM, "min": RFX_AGG_MIN, "max": RFX_AGG_MAX, "count": RFX_AGG_COUNT, "avg": RFX_AGG_AVG,
-        "first": RFX_AGG_FIRST}
+        "first": RFX_AGG_FIRST, "last": RFX_AGG_LAST}
 
 
 class RfxError(RuntimeError):
@@ -279,6 +279,11 @@ PROTOTYPES = {
     "rfx_hip_group_median": (C.c_int, [_ctx, _P(MedRows), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     "rfx_hip_median": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(Value)]),
     "rfx_hip_median_keys": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "rfx_hip_last_rows": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_last_gather": (C.c_int, [_ctx, _P(C.c_void_p), _P(C.c_int64), _P(C.c_int64), C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_dev_derive": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rfx_hip_dev_finalise": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, _P(Value)]),
     "rfx_hip_key_slot_table": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "rfx_hip_sort_index": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "rfx_hip_sort_values": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
@@ -354,6 +359,8 @@ EXEC_PROTOTYPES = {
     "rfx_exec_probe_handover_us": (C.c_double, [C.c_int, C.c_int]),
     "rfx_exec_median": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_int32, _P(Value)]),
     "rfx_exec_group_median": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rfx_exec_dev": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_int32, _P(Value)]),
+    "rfx_exec_group_dev": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rfx_exec_sort": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_exec_sort_values": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),

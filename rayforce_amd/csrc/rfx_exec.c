@@ -85,6 +85,7 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_groupby.c"
 #include "rfx_exec_result.c"
 #include "rfx_exec_median.c"
+#include "rfx_exec_lastdev.c"
 #include "rfx_exec_sort.c"
 #include "rfx_exec_asof.c"
 #include "rfx_exec_window.c"

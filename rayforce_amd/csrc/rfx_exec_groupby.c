@@ -682,7 +682,8 @@ static int rowhash_proof_passes(rfx_exec_t *x, const rfx_query_t *q, int64_t cap
     }
     return rc;
 }
-int rfx_exec_group_by(rfx_exec_t *x, const rfx_query_t *q, rfx_groups_t *out) {
+/* (rfx_exec_group_by itself: rfx_exec_lastdev.c -- LAST aggregates are rewritten there, every other query comes straight here) */
+static int group_by_query(rfx_exec_t *x, const rfx_query_t *q, rfx_groups_t *out) {
     if (!x || !q || !out || q->nkeys < 1 || q->nkeys > RFX_MAX_KEYS || !q->d_keys || q->nagg < 0 || q->nagg > RFX_EXEC_MAX_AGGS || q->npred < 0 || q->npred > RFX_MAX_PREDS)
         return RFX_EINVAL;
     rfx_hip_ctx_bind_thread(x->ctx[0]);

@@ -75,6 +75,11 @@ int rfx_exec_filter_aggr(rfx_exec_t *x, const rfx_query_t *q, rfx_value_t *value
         snprintf(x->err, sizeof(x->err), "rfx_exec: a selection by row ids stands alone (no comparisons, no mask) inside one process");
         return RFX_EINVAL;
     }
+    for (int a = 0; a < q->nagg && exch; a++)
+        if (q->aggs && q->aggs[a].kind == RFX_AGG_LAST) { /* (positions are local to a process, and only FIRST's rank rule is written down below) */
+            snprintf(x->err, sizeof(x->err), "rfx_exec: last over several processes is not covered");
+            return RFX_ELIMIT;
+        }
     rfx_hip_ctx_bind_thread(x->ctx[0]);
     x->stat[RFX_XSTAT_QUERIES]++;
     x->err[0] = 0;
@@ -99,7 +104,7 @@ int rfx_exec_filter_aggr(rfx_exec_t *x, const rfx_query_t *q, rfx_value_t *value
         if (rc == RFX_OK) {
             rfx_partial_t acc[RFX_MAX_AGGS + 1];
             memcpy(acc, sh[0].part, sizeof(rfx_partial_t) * (size_t)(na + 1));
-            for (int s = 1; s < S; s++) { /* shard order = row order: FIRST keeps the lowest row, f64 sums add in a fixed order */
+            for (int s = 1; s < S; s++) { /* shard order = row order: FIRST keeps the lowest row, LAST the highest, f64 sums add in a fixed order */
                 for (int a = 0; a < na; a++) rfx_partial_merge(sh[0].aggs[a].kind, rfx_agg_input_type(&sh[0].aggs[a]), &acc[a], &sh[s].part[a]);
                 rfx_partial_merge(RFX_AGG_COUNT, RFX_I64, &acc[na], &sh[s].part[na]);
             }

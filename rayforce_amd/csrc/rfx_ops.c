@@ -51,21 +51,20 @@ static struct {
     /* the host's own built-ins, for recognising function objects inside parsed expressions and for delegation */
     void *f[64];
 } H;
-/* F_SUM .. F_FIRST are the aggregates rfx_select / rfx_update map (they test that id RANGE); the ids after F_BINR are not: F_LAST is recognised by
- * window_agg (rfx_ops_window.c) alone, and every other reader of fn_id must keep refusing it; F_DISTINCT .. F_UNION (and F_IN as a verb of its own) are the
- * set verbs of rfx_ops_set.c: no reader of fn_id maps them -- inside where: F_IN stays the comparison list of rfx_ops_plan.c and nothing else */
-enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_N };
+/* F_SUM .. F_FIRST are the aggregates rfx_update maps: it tests that id RANGE.  rfx_select maps the same range and, by name, F_LAST, F_MED and F_DEV.
+ * The ids after F_BINR lie outside the range: window_agg (rfx_ops_window.c) recognises F_LAST and refuses F_DEV; F_DISTINCT .. F_UNION (and F_IN as a
+ * verb of its own) are the set verbs of rfx_ops_set.c, which no reader of fn_id maps -- inside where: F_IN stays the comparison list of
+ * rfx_ops_plan.c and nothing else. */
+enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_DEV, F_N };
 static const char *HOST_FN[F_N] = {"ray_sum", "ray_avg", "ray_min", "ray_max", "ray_count", "ray_first", "ray_eq",  "ray_ne",  "ray_lt",  "ray_gt",
                                    "ray_le",  "ray_ge",  "ray_and", "ray_or",  "ray_select", "ray_add",  "ray_sub", "ray_mul", "ray_fdiv", "ray_div", "ray_mod", "ray_xbar",
                                    "ray_left_join", "ray_inner_join", "ray_update", "ray_take", "ray_in", "ray_within", "ray_not", "ray_med",
                                    "ray_iasc", "ray_idesc", "ray_asc", "ray_desc", "ray_rank", "ray_xasc", "ray_xdesc",
                                    "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last",
-                                   "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union"}; /* (in / within / not: recognised inside where: only; last: inside a window join's aggregates only) */
+                                   "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union", "ray_dev"}; /* (in / within / not: recognised inside where: only) */
 /* xbar is recognised inside `by:` only; the standalone object model still needs a distinct function object for it:
  * this stub is never called by this library. */
 static obj_p x_stub_xbar(obj_p a, obj_p b) { (void)a; (void)b; return NULL; }
-/* ... and so does last, recognised as (last column) among a window join's aggregates only */
-static obj_p x_stub_last(obj_p a) { (void)a; return NULL; }
 static void *OUR_FN[F_N];
 static void *g_host_where, *g_host_at, *g_host_group; /* the host's built-ins behind rfx_where / rfx_at / rfx_group (NULL without a host) */
 static char g_err[640];
@@ -87,7 +86,7 @@ int rfx_host_bind(void) {
     OUR_FN[F_IASC] = (void *)rfx_iasc; OUR_FN[F_IDESC] = (void *)rfx_idesc; OUR_FN[F_ASC] = (void *)rfx_asc; OUR_FN[F_DESC] = (void *)rfx_desc;
     OUR_FN[F_RANK] = (void *)rfx_rank; OUR_FN[F_XASC] = (void *)rfx_xasc; OUR_FN[F_XDESC] = (void *)rfx_xdesc;
     OUR_FN[F_AJ] = (void *)rfx_asof_join; OUR_FN[F_BIN] = (void *)rfx_bin; OUR_FN[F_BINR] = (void *)rfx_binr;
-    OUR_FN[F_WJ] = (void *)rfx_window_join; OUR_FN[F_WJ1] = (void *)rfx_window_join1; OUR_FN[F_LAST] = (void *)x_stub_last;
+    OUR_FN[F_WJ] = (void *)rfx_window_join; OUR_FN[F_WJ1] = (void *)rfx_window_join1; OUR_FN[F_LAST] = (void *)rfx_last; OUR_FN[F_DEV] = (void *)rfx_dev;
     OUR_FN[F_IN] = (void *)rfx_in; OUR_FN[F_DISTINCT] = (void *)rfx_distinct; OUR_FN[F_FIND] = (void *)rfx_find; OUR_FN[F_SECT] = (void *)rfx_sect;
     OUR_FN[F_EXCEPT] = (void *)rfx_except; OUR_FN[F_UNION] = (void *)rfx_union;
     void *v = dlsym(RTLD_DEFAULT, "vector"), *t = dlsym(RTLD_DEFAULT, "table"), *e = dlsym(RTLD_DEFAULT, "eval");
@@ -138,7 +137,7 @@ obj_p rfx_host_fn(const char *name) {
         {"and", F_AND, RFX_TYPE_VARY, RFX_FN_SPECIAL_FORM}, {"or", F_OR, RFX_TYPE_VARY, RFX_FN_SPECIAL_FORM}, {"select", F_SELECT, RFX_TYPE_UNARY, 0},
         {"+", F_ADD, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"-", F_SUB, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"*", F_MUL, RFX_TYPE_BINARY, RFX_FN_ATOMIC},
         {"div", F_FDIV, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"/", F_DIV, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"%", F_MOD, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"xbar", F_XBAR, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"update", F_UPDATE, RFX_TYPE_UNARY, 0},
-        {"med", F_MED, RFX_TYPE_UNARY, RFX_FN_AGGR},
+        {"med", F_MED, RFX_TYPE_UNARY, RFX_FN_AGGR}, {"dev", F_DEV, RFX_TYPE_UNARY, RFX_FN_AGGR},
         {"iasc", F_IASC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"idesc", F_IDESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"asc", F_ASC, RFX_TYPE_UNARY, RFX_FN_NONE},
         {"desc", F_DESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"rank", F_RANK, RFX_TYPE_UNARY, RFX_FN_NONE}, {"xasc", F_XASC, RFX_TYPE_BINARY, RFX_FN_NONE},
         {"xdesc", F_XDESC, RFX_TYPE_BINARY, RFX_FN_NONE},

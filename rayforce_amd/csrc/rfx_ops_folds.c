@@ -106,6 +106,32 @@ static obj_p fold_mapgroup(int f, int kind, obj_p x) {
         a.d_col = dv;
         a.col_type = col_ctype(val);
         a.kind = kind;
+        if (kind == RFX_AGG_LAST) { /* planned (rfx_exec_group_by turns it into a MAX over derived rows): the same dense group-by, the same group order */
+            rfx_query_t Q;
+            memset(&Q, 0, sizeof(Q));
+            const void *dkeys[1] = {dk};
+            Q.aggs = &a;
+            Q.nagg = 1;
+            Q.logic = RFX_AND;
+            Q.nkeys = 1;
+            Q.d_keys = dkeys;
+            Q.nrows = n;
+            rfx_groups_t R;
+            if (rfx_exec_group_by(g_x, &Q, &R) != RFX_OK) { res = fail(rfx_exec_last_error(g_x)[0] ? rfx_exec_last_error(g_x) : rfx_hip_last_error()); goto done; }
+            if (R.groups != groups) {
+                rfx_exec_groups_free(g_x, &R);
+                why = "group count of the index does not match its rows";
+                goto out;
+            }
+            obj_p outl = H.vector(out_f64 ? RFX_TYPE_F64 : RFX_TYPE_I64, groups);
+            const void *srcs[1] = {R.d_results[0]};
+            void *dsts[1] = {RFX_AS_RAW(outl)};
+            const int frc = rfx_exec_groups_fetch_all(g_x, &R, 1, srcs, dsts);
+            rfx_exec_groups_free(g_x, &R);
+            if (frc != RFX_OK) { H.drop(outl); res = fail_hip("group emit"); goto done; }
+            res = outl;
+            goto done;
+        }
         int narr = 0;
         rfx_hip_group_table_arrays(&a, 1, &narr);
         void *store = NULL;
@@ -434,6 +460,9 @@ rfx_obj_p rfx_min(rfx_obj_p x) { return fold_op(F_MIN, RFX_AGG_MIN, x); }
 rfx_obj_p rfx_max(rfx_obj_p x) { return fold_op(F_MAX, RFX_AGG_MAX, x); }
 rfx_obj_p rfx_count(rfx_obj_p x) { return fold_op(F_COUNT, RFX_AGG_COUNT, x); }
 rfx_obj_p rfx_first(rfx_obj_p x) { return fold_op(F_FIRST, RFX_AGG_FIRST, x); }
+/* ray_last: a vector's last cell (at_idx(x, len - 1), core/items.c:1112-1114), a MAPFILTER pair's last collected cell -- positional, null or not -- and per
+ * group of a MAPGROUP pair the last non-null cell (aggr_last with one chunk, core/aggr.c:851-930) */
+rfx_obj_p rfx_last(rfx_obj_p x) { return fold_op(F_LAST, RFX_AGG_LAST, x); }
 
 /* ---- (med x): ray_med (core/math.c:2529-2626) -- an I64 vector or a MAPFILTER over one (filter_collect, then the scalar rule), a MAPGROUP over I64 /
  * TIMESTAMP / F64 values (aggr_med: the grouped rule) -- exact medians on the device (rfx_median.hip).  (ray_med itself reaches neither lazy arm: its
@@ -536,6 +565,119 @@ done:
 rfx_obj_p rfx_med(rfx_obj_p x) {
     op_begin();
     obj_p r = med_impl(x);
+    op_end();
+    return r;
+}
+
+/* ---- (dev x): ray_dev (core/math.c:2628-2699) -- an I64 / F64 vector or a MAPFILTER over one (filter_collect, then the two passes of the scalar rule), a
+ * MAPGROUP over I64 / TIMESTAMP / F64 values (aggr_dev: the grouped rule, core/aggr.c:2250-2350,2864-2929) -- on the device (rfx_lastdev.hip).  (ray_dev
+ * itself reaches neither lazy arm, as ray_med: its l = ray_cnt(x)->i64 reads such a pair's count as 0 and answers null; a host that registers this
+ * function as its own `dev` aggregate gets the deviations those arms compute.  rfx_select follows ray_select and leaves dev under by: / where: to the
+ * host.)  The MAPGROUP's value and key columns are prepared as fold_mapgroup prepares them; the three sums per group ride through the planner's group-by
+ * (rfx_exec_group_dev).  Everything else -- other types, parted / window indexes, sharded columns -- is the host's own ray_dev. */
+static obj_p dev_host(obj_p x, const char *why) {
+    if (H.bound == 1 && H.f[F_DEV]) return HOST_CALL(((rfx_unary_f)H.f[F_DEV])(x));
+    char b[256];
+    snprintf(b, sizeof(b), "dev: not covered by the MI355X path (%s) and no host ray_dev to delegate to", why);
+    return fail(b);
+}
+static obj_p dev_impl(obj_p x) {
+    rfx_host_bind();
+    if (!x) return fail("dev: null argument");
+    const int mg = x->type == RFX_TYPE_MAPGROUP, mf = x->type == RFX_TYPE_MAPFILTER;
+    obj_p val = (mg || mf) ? RFX_AS_LIST(x)[0] : x;
+    if (!(val->type == RFX_TYPE_I64 || val->type == RFX_TYPE_F64 || (mg && val->type == RFX_TYPE_TIMESTAMP))) return dev_host(x, "value type");
+    if (mf && RFX_AS_LIST(x)[1]->type != RFX_TYPE_I64) return dev_host(x, "filter ids");
+    if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
+    if (g_nshards > 1) return dev_host(x, "sharded columns");
+    void *tmp[4] = {0};
+    int ntmp = 0;
+    obj_p res = NULL;
+    const void *dv = NULL;
+    if (resident(val, 0, &dv) != RFX_OK) return fail_hip("column upload");
+    if (!mg) { /* the scalar rule over the vector, or over the values at the filter's ids */
+        int64_t n = val->len;
+        if (mf) {
+            obj_p ids = RFX_AS_LIST(x)[1];
+            const void *di;
+            n = ids->len;
+            if (transient(ids, &di) != RFX_OK || rfx_hip_malloc(g_ctx, &tmp[ntmp], (size_t)(n ? n : 1) * 8) != RFX_OK) return fail_hip("filter upload");
+            ntmp++;
+            if (rfx_hip_gather_checked(g_ctx, dv, val->len, col_ctype(val), (const int64_t *)di, n, tmp[0]) != RFX_OK) { res = fail_hip("gather"); goto done; }
+            dv = tmp[0];
+        }
+        rfx_value_t v;
+        if (rfx_hip_dev(g_ctx, dv, col_ctype(val), n, &v) != RFX_OK) { res = fail_hip("dev"); goto done; }
+        res = H.f64(v.f);
+        goto done;
+    }
+    {
+        obj_p index = RFX_AS_LIST(x)[1];
+        if (!index || index->type != RFX_TYPE_LIST || index->len != 7) return fail("dev: malformed group index");
+        obj_p *ix = RFX_AS_LIST(index);
+        const int64_t itype = ix[0]->i64, groups = ix[1]->i64;
+        obj_p gids = ix[2], source = ix[4], filter = ix[5];
+        if (itype != RFX_INDEX_TYPE_IDS && itype != RFX_INDEX_TYPE_SHIFT) return dev_host(x, "parted / window index");
+        if (!gids || gids->type != RFX_TYPE_I64 || groups < 0) return dev_host(x, "group ids");
+        if (itype == RFX_INDEX_TYPE_SHIFT && !(source && source->type > 0 && col_ctype(source) == RFX_I64)) return dev_host(x, "source column");
+        const int filtered = filter && filter->type == RFX_TYPE_I64;
+        const int64_t n = filtered ? filter->len : (itype == RFX_INDEX_TYPE_IDS ? gids->len : source->len);
+        if (itype == RFX_INDEX_TYPE_IDS && gids->len != n) return fail("dev: group ids / filter length mismatch");
+        if (!filtered && val->len != n) return fail("length");
+        if (groups == 0 || n == 0) return H.vector(RFX_TYPE_F64, 0);
+        if (itype == RFX_INDEX_TYPE_SHIFT && gids->len <= 0) return dev_host(x, "empty key table"); /* (before any device scratch is taken) */
+        const void *dfl = NULL, *dk = NULL;
+        if (filtered) {
+            if (transient(filter, &dfl) != RFX_OK || rfx_hip_malloc(g_ctx, &tmp[ntmp], (size_t)n * 8) != RFX_OK) { res = fail_hip("filter upload"); goto done; }
+            ntmp++;
+            if (rfx_hip_gather_checked(g_ctx, dv, val->len, col_ctype(val), (const int64_t *)dfl, n, tmp[0]) != RFX_OK) { res = fail_hip("gather"); goto done; }
+            dv = tmp[0];
+        }
+        if (itype == RFX_INDEX_TYPE_IDS) {
+            if (transient(gids, &dk) != RFX_OK) { res = fail_hip("group ids upload"); goto done; }
+        } else {
+            if (resident(source, 0, &dk) != RFX_OK) { res = fail_hip("column upload"); goto done; }
+            if (filtered) {
+                if (rfx_hip_malloc(g_ctx, &tmp[ntmp], (size_t)n * 8) != RFX_OK) { res = fail_hip("scratch"); goto done; }
+                if (rfx_hip_gather_checked(g_ctx, dk, source->len, RFX_I64, (const int64_t *)dfl, n, tmp[ntmp]) != RFX_OK) { ntmp++; res = fail_hip("gather"); goto done; }
+                dk = tmp[ntmp++];
+            }
+        }
+        void *dout = NULL;
+        if (rfx_hip_malloc(g_ctx, &dout, (size_t)groups * 8) != RFX_OK) { res = fail_hip("result"); goto done; }
+        tmp[ntmp++] = dout;
+        rfx_query_t Q;
+        memset(&Q, 0, sizeof(Q));
+        const void *dkeys[1] = {dk};
+        Q.logic = RFX_AND;
+        Q.nkeys = 1;
+        Q.d_keys = dkeys;
+        Q.nrows = n;
+        rfx_groups_t G; /* (the index says how many groups the rows make: rfx_exec_group_dev checks its own group-by against it) */
+        memset(&G, 0, sizeof(G));
+        G.groups = groups;
+        G.nkeys = 1;
+        const int drc = rfx_exec_group_dev(g_x, &Q, &G, dv, col_ctype(val), dout);
+        if (drc == RFX_ESTATE) {
+            for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
+            return dev_host(x, "group count of the index does not match its rows");
+        }
+        if (drc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)[0] ? rfx_exec_last_error(g_x) : rfx_hip_last_error()); goto done; }
+        obj_p out = H.vector(RFX_TYPE_F64, groups);
+        if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), dout, (size_t)groups * 8) != RFX_OK) {
+            H.drop(out);
+            res = fail_hip("dev over a MAPGROUP");
+            goto done;
+        }
+        res = out;
+    }
+done:
+    for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
+    return res;
+}
+rfx_obj_p rfx_dev(rfx_obj_p x) {
+    op_begin();
+    obj_p r = dev_impl(x);
     op_end();
     return r;
 }

@@ -43,6 +43,10 @@ typedef struct {
      * answer instead (F64) */
     unsigned char med[RFX_MAX_AGGS];
     int nmed;
+    /* (dev column): the same stand-in; its cell is rfx_exec_dev's answer (F64) */
+    unsigned char dev[RFX_MAX_AGGS];
+    int ndev;
+    int nlast; /* (last column) mappings: RFX_AGG_LAST */
 } sel_maps_t;
 /* result cells of an aggregate over a widened 4-byte column, back in the column's own width: the i64 null and the i64 identities of an
  * all-null group (core/aggr.c:1246) become the 4-byte ones */
@@ -64,6 +68,9 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
     memset(M->det_avg, 0, sizeof(M->det_avg));
     memset(M->med, 0, sizeof(M->med));
     M->nmed = 0;
+    memset(M->dev, 0, sizeof(M->dev));
+    M->ndev = 0;
+    M->nlast = 0;
     for (int64_t i = 0; i < dkeys->len; i++) {
         int64_t k = RFX_AS_I64(dkeys)[i];
         if (k == s_from || k == s_where || k == s_by || k == s_take) continue;
@@ -97,13 +104,39 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
             M->names[M->nagg++] = k;
             continue;
         }
-        if (f < F_SUM || f > F_FIRST) { *why = "mapping is not (aggr ...)"; return SEL_OUT; }
+        if (f == F_DEV) {
+            /* (dev column): scalar over an I64 / TIMESTAMP / F64 column, no where: -- ray_dev of the column itself.  Under by: and under where: ray_dev's
+             * first step is med's, l = ray_cnt(x)->i64 (core/math.c:2629), which reads the count of a MAPGROUP / MAPFILTER pair as 0 (core/math.c:1832):
+             * the reference answers null in every cell there, before its own TYPE_MAPGROUP arm.  Those shapes stay the host's; the real grouped and filtered
+             * deviations are rfx_dev's. */
+            if (a->type != -RFX_TYPE_SYMBOL) { *why = "dev of an expression"; return SEL_OUT; }
+            if (grouped) { *why = "dev under by: (ray_dev of a MAPGROUP pair answers null in the reference)"; return SEL_OUT; }
+            obj_p c = table_col(tab, a->i64);
+            if (!c || (g_npx && proxy_of(c)) || !(c->type == RFX_TYPE_I64 || c->type == RFX_TYPE_TIMESTAMP || c->type == RFX_TYPE_F64)) {
+                *why = "dev: column type";
+                return SEL_OUT;
+            }
+            const void *d;
+            if (resident(c, 0, &d) != RFX_OK) return SEL_DONE;
+            memset(&M->aggs[n], 0, sizeof(M->aggs[n]));
+            M->aggs[n].kind = RFX_AGG_COUNT;
+            M->aggs[n].d_col = d;
+            M->aggs[n].col_type = col_ctype(c);
+            M->outtype[n] = RFX_TYPE_F64;
+            M->dev[n] = 1;
+            M->ndev++;
+            M->names[M->nagg++] = k;
+            continue;
+        }
+        if ((f < F_SUM || f > F_FIRST) && f != F_LAST) { *why = "mapping is not (aggr ...)"; return SEL_OUT; }
         memset(&M->aggs[n], 0, sizeof(M->aggs[n]));
-        M->aggs[n].kind = KIND[f - F_SUM];
+        M->aggs[n].kind = f == F_LAST ? RFX_AGG_LAST : KIND[f - F_SUM];
+        M->nlast += f == F_LAST;
         if (a->type == RFX_TYPE_LIST && a->len == 3) {
             /* (aggr expr), expr = (op x y) over columns, atoms and nested expressions: folded on the device.  (count expr)
              * answers the number of groups in the reference and (first expr) under by: is a `length` error there: the host's */
             if (f == F_COUNT || f == F_FIRST) { *why = "count / first of an expression"; return SEL_OUT; }
+            if (f == F_LAST) { *why = "last of an expression"; return SEL_OUT; }
             int nn = 0, ncols = 0;
             int top = build_xnodes(tab, a, M->xnodes[n], &nn, &ncols, why);
             if (top == -2) return SEL_DONE;
@@ -118,10 +151,10 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
         }
         if (a->type != -RFX_TYPE_SYMBOL) { *why = "mapping is not (aggr column)"; return SEL_OUT; }
         obj_p c = table_col(tab, a->i64);
-        /* a 4-byte integer column (I32 / DATE / TIME): min / max / first / count / sum fold its widened device copy and the result cells
+        /* a 4-byte integer column (I32 / DATE / TIME): min / max / first / last / count / sum fold its widened device copy and the result cells
          * are narrowed back (sel_narrow_i32); avg and the sum of dates are the host's */
         const int narrow = c && IS_I32_FAMILY(c->type) && !(g_npx && proxy_of(c)) && !(grouped && c->type == RFX_TYPE_I32) && /* (any grouped aggregate over an I32 column is a `type` error in the reference: its to say) */
-                           ((f == F_MIN || f == F_MAX || f == F_FIRST || f == F_COUNT) ||
+                           ((f == F_MIN || f == F_MAX || f == F_FIRST || f == F_LAST || f == F_COUNT) ||
                             /* sums of I32 / TIME columns wrap in 32 bits there (FOLD_ADDI32 / ADDI32, core/math.c:1864-1871, core/aggr.c:1095-1100):
                              * the low 32 bits of the 64-bit sum of the widened column are that sum */
                             (f == F_SUM && !grouped && (c->type == RFX_TYPE_I32 || c->type == RFX_TYPE_TIME))); /* (grouped: a `type` error there) */
@@ -613,6 +646,16 @@ static obj_p select_impl(obj_p dict) {
             if (g_nshards > 1) { why = "med over a sharded table"; goto out; }
             if (rfx_exec_ranks(g_x, NULL) > 1) { why = "med over several ranks"; goto out; }
         }
+        if (M.ndev) { /* dev: as med */
+            if (where) { why = "dev under where: (ray_dev of a MAPFILTER pair answers null in the reference)"; goto out; }
+            if (parted) { why = "dev over a parted table"; goto out; }
+            if (g_nshards > 1) { why = "dev over a sharded table"; goto out; }
+            if (rfx_exec_ranks(g_x, NULL) > 1) { why = "dev over several ranks"; goto out; }
+        }
+        if (M.nlast) { /* last: the shards of one device, one process (the planner refuses the rest; said here, before anything runs) */
+            if (parted) { why = "last over a parted table"; goto out; }
+            if (rfx_exec_ranks(g_x, NULL) > 1) { why = "last over several ranks"; goto out; }
+        }
         /* by: a column symbol, or a dict {name: column ...} (get_gkeys / get_gvals, core/query.c:165-240) */
         obj_p kcs[RFX_MAX_KEYS] = {0};
         const void *dks[RFX_MAX_KEYS] = {0};
@@ -724,7 +767,7 @@ static obj_p select_impl(obj_p dict) {
             tm_mark();
             if (grc == RFX_EXEC_NULL_KEY) { why = "null group key"; goto out; }
             if (grc == RFX_ESTATE && strstr(rfx_exec_last_error(g_x), "collision")) { why = "row-hash collision between two key tuples"; goto out; }
-            if (grc == RFX_ELIMIT && g_nshards > 1) { why = "sharded table: shape the planner runs on one shard"; goto out; }
+            if (grc == RFX_ELIMIT && g_nshards > 1) { why = M.nlast ? "sharded table: last under by: runs on the shards of one device" : "sharded table: shape the planner runs on one shard"; goto out; }
             if (grc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
             const sel_keys_t K = {nkeys, key_out_type, kenum, kcs};
             rfx_groups_t Rw;
@@ -751,6 +794,12 @@ static obj_p select_impl(obj_p dict) {
             const int mrc = rfx_exec_median(g_x, &Q, M.aggs[a].d_col, M.aggs[a].col_type, &vals[a]);
             if (mrc == RFX_ENOMEM) { why = "med: device scratch (8 B per row) not available"; goto out; }
             if (mrc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
+        }
+        for (int a = 0; a < M.nagg; a++) {
+            if (!M.dev[a]) continue;
+            const int drc = rfx_exec_dev(g_x, &Q, M.aggs[a].d_col, M.aggs[a].col_type, &vals[a]);
+            if (drc == RFX_ENOMEM) { why = "dev: device scratch not available"; goto out; }
+            if (drc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
         }
         res = sel_build_scalar(vals, &M);
         g_last_gpu = 1;

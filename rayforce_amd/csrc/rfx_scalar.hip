@@ -106,9 +106,78 @@ launched:
     return RFX_OK;
 }
 
+// ---- LAST (ray_last: the cell at the last selected row, null or not -- at_idx(x, len - 1), core/items.c:1112-1114) ----
+// The fused fold above does not carry it: a further kind in acc_update / acc_combine moves the register allocation of instantiations that serve plans
+// without any `last` in them (measured: docs/ledger_r07.md).  It does not need the fold either.  The last selected row is nrows - 1 without predicates;
+// with predicates it is the last id of the ordered compaction (rfx_hip_where_begin / _emit: the predicate columns once more, 8 B per selected row).
+// k_last_fill then writes, per LAST aggregate, the partial {pos = global row, ext = the column's cell there, cnt = 1} -- the identity when nothing is
+// selected -- into its slot of the fold's output; the other aggregates of the call run through the fold as ever, with a COUNT standing in.
+struct LastFill {
+    int n;
+    int slot[RFX_MAX_AGGS];
+    const u64 *col[RFX_MAX_AGGS];
+};
+__global__ void k_last_fill(const LastFill F, const i64 *__restrict__ d_ids, i64 count, i64 lastrow, i64 row0, rfx_partial_t *__restrict__ out) {
+    const int a = threadIdx.x;
+    if (a >= F.n) return;
+    const i64 L = d_ids ? (count > 0 ? d_ids[count - 1] : -1) : lastrow;
+    rfx_partial_t o;
+    o.isum = 0;
+    o.fsum = 0.0;
+    o.cnt = 0;
+    o.ext = 0;
+    o.pos = RFX_INF_I64_D;
+    o._rsv[0] = o._rsv[1] = o._rsv[2] = 0;
+    if (L >= 0) {
+        o.pos = row0 + L;
+        o.ext = (i64)F.col[a][L];
+        o.cnt = 1;
+    }
+    out[F.slot[a]] = o;
+}
+
+static int rfx_filter_aggr_with_last(rfx_ctx_t *c, const rfx_pred_t *preds, int npred, int logic, const rfx_agg_t *aggs, int nagg, int64_t nrows, int64_t row0,
+                                     rfx_partial_t *d_out) {
+    RFX_REQUIRE(nagg <= RFX_MAX_AGGS, RFX_ELIMIT, "too many aggregates");
+    rfx_agg_t rest[RFX_MAX_AGGS];
+    LastFill F;
+    memset(&F, 0, sizeof(F));
+    for (int a = 0; a < nagg; a++) {
+        rest[a] = aggs[a];
+        if (aggs[a].kind != RFX_AGG_LAST) continue;
+        RFX_REQUIRE(aggs[a].xop == RFX_X_NONE && aggs[a].nxnodes == 0, RFX_EINVAL, "last of an expression is not supported");
+        RFX_REQUIRE(aggs[a].d_col != NULL || nrows == 0, RFX_EINVAL, "aggregate column is NULL");
+        RFX_REQUIRE(aggs[a].col_type == RFX_I64 || aggs[a].col_type == RFX_F64, RFX_EINVAL, "aggregate column type must be i64 or f64");
+        memset(&rest[a], 0, sizeof(rest[a]));
+        rest[a].kind = RFX_AGG_COUNT;
+        F.slot[F.n] = a;
+        F.col[F.n++] = (const u64 *)aggs[a].d_col;
+    }
+    int rc = rfx_hip_filter_aggr(c, preds, npred, logic, rest, nagg, nrows, row0, d_out);
+    if (rc != RFX_OK) return rc;
+    void *ids = NULL;
+    int64_t count = 0;
+    if (npred > 0 && nrows > 0) {
+        rc = rfx_hip_where_begin(c, preds, npred, logic, NULL, nrows, &count);
+        if (rc == RFX_OK && count > 0) rc = rfx_hip_malloc(c, &ids, (size_t)count * 8);
+        if (rc == RFX_OK && count > 0) rc = rfx_hip_where_emit(c, 0, (int64_t *)ids);
+        if (rc != RFX_OK) {
+            if (ids) rfx_hip_free(c, ids);
+            return rc;
+        }
+    }
+    hipLaunchKernelGGL(k_last_fill, dim3(1), dim3(RFX_WAVE), 0, c->stream, F, (const i64 *)ids, (i64)count, (i64)(npred > 0 ? -1 : nrows - 1), (i64)row0, d_out);
+    const hipError_t e = hipGetLastError();
+    if (ids) rfx_hip_free(c, ids); // (the pool hands a block out again in stream order: after the launch above)
+    RFX_HIP_CHECK(e);
+    return RFX_OK;
+}
+
 extern "C" int rfx_hip_filter_aggr(rfx_ctx_t *c, const rfx_pred_t *preds, int npred, int logic, const rfx_agg_t *aggs,
                                    int nagg, int64_t nrows, int64_t row0, rfx_partial_t *d_out) {
     RFX_REQUIRE(c && d_out, RFX_EINVAL, "NULL argument");
+    for (int a = 0; aggs && a < nagg; a++)
+        if (aggs[a].kind == RFX_AGG_LAST) return rfx_filter_aggr_with_last(c, preds, npred, logic, aggs, nagg, nrows, row0, d_out);
     Plan P;
     int rc = rfx_plan_build(&P, preds, npred, logic, aggs, nagg, NULL, NULL, nrows, row0);
     if (rc == RFX_ELIMIT && nagg > 1) {
@@ -202,6 +271,13 @@ extern "C" void rfx_partial_merge(int kind, int col_type, rfx_partial_t *into, c
                 into->cnt = from->cnt;
             }
             break;
+        case RFX_AGG_LAST: // the highest row wins
+            if (from->cnt > 0 && (into->cnt == 0 || from->pos > into->pos)) {
+                into->pos = from->pos;
+                into->ext = from->ext;
+                into->cnt = from->cnt;
+            }
+            break;
         default:
             break;
     }
@@ -242,6 +318,16 @@ extern "C" int rfx_agg_finalize(int kind, int col_type, const rfx_partial_t *p, 
                 else out->f = (double)p->isum / (double)p->cnt;
             }
             return RFX_OK;
+        case RFX_AGG_LAST: // (mirrors FIRST: an empty selection gives the typed null)
+            out->type = f ? RFX_F64 : RFX_I64;
+            if (p->cnt == 0) {
+                out->is_null = 1;
+                out->i = f ? (int64_t)RFX_NAN_BITS : RFX_NULL_I64_D;
+            } else {
+                out->i = p->ext;
+                out->is_null = f ? (bits_f64(p->ext) != bits_f64(p->ext)) : (p->ext == RFX_NULL_I64_D);
+            }
+            return RFX_OK;
         case RFX_AGG_FIRST:
             out->type = f ? RFX_F64 : RFX_I64;
             if (p->pos == RFX_INF_I64_D) {
@@ -266,11 +352,23 @@ extern "C" int rfx_hip_filter_aggr_host(rfx_ctx_t *c, const rfx_pred_t *preds, i
     int rc = rfx_ws_reserve(c, (size_t)rfx_scalar_grid(c) * 9 * sizeof(Acc) + bytes + 256);
     if (rc != RFX_OK) return rc;
     rfx_partial_t *d_out = (rfx_partial_t *)((char *)c->d_ws + (((size_t)rfx_scalar_grid(c) * 9 * sizeof(Acc) + 255) & ~(size_t)255));
+    void *own = NULL; // with a LAST aggregate the `where` pass behind it may regrow the workspace: the partials then live in a block of their own
+    for (int a = 0; aggs && a < nagg && !own; a++)
+        if (aggs[a].kind == RFX_AGG_LAST) {
+            rc = rfx_hip_malloc(c, &own, bytes);
+            if (rc != RFX_OK) return rc;
+            d_out = (rfx_partial_t *)own;
+        }
     rc = rfx_hip_filter_aggr(c, preds, npred, logic, aggs, nagg, nrows, 0, d_out);
-    if (rc != RFX_OK) return rc;
+    if (rc != RFX_OK) {
+        if (own) rfx_hip_free(c, own);
+        return rc;
+    }
     rfx_partial_t *h = (rfx_partial_t *)c->h_pin;
-    RFX_HIP_CHECK(hipMemcpyAsync(h, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    RFX_HIP_CHECK(hipStreamSynchronize(c->stream));
+    hipError_t ce = hipMemcpyAsync(h, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (ce == hipSuccess) ce = hipStreamSynchronize(c->stream);
+    if (own) rfx_hip_free(c, own);
+    RFX_HIP_CHECK(ce);
     for (int a = 0; a < nagg; a++) {
         rc = rfx_agg_finalize(aggs[a].kind, rfx_agg_input_type(&aggs[a]), &h[a], &values[a]);
         if (rc != RFX_OK) return rc;

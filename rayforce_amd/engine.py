@@ -274,6 +274,15 @@ class Engine:
     def avg(self, col, where=None, table=None): return self.filter_aggr([("avg", col)], where, table)[0][0]
     def count(self, col, where=None, table=None): return self.filter_aggr([("count", col)], where, table)[0][0]
     def first(self, col, where=None, table=None): return self.filter_aggr([("first", col)], where, table)[0][0]
+    def last(self, col, where=None, table=None): return self.filter_aggr([("last", col)], where, table)[0][0]
+
+    def dev(self, col, where=None, table=None) -> float:
+        """``(dev col)`` over the selection: ray_dev's two passes (core/math.c:2628-2699) -- NaN for no non-null cell, 0.0 for one.  (syncs)"""
+        c = self._check_col(self._resolve(col, table))
+        q, _ = self._query(where, [], table, c.numel())
+        v = L.Value()
+        self._xcheck(self.lib.rfx_exec_dev(self._x, C.byref(q), c.data_ptr(), _ctype_of(c), C.byref(v)), "dev")
+        return self._value(v)
 
     # ------------------------------------------------------------------ K2: masks (API parity with the reference's B8 results)
     def cmp(self, op: str, lhs, rhs, table=None) -> torch.Tensor:
@@ -419,6 +428,23 @@ class Engine:
             r["results"] = [x[perm] for x in r["results"]]
             r["key_columns"] = [x[perm] for x in r["key_columns"]]
         return r
+
+    def group_dev(self, key, col, where=None, table=None, flags: int = 0):
+        """``(dev col)`` per group of ``select ... from t [where p] by key`` -> dict(groups=, keys=, dev=) of device tensors, groups in
+        first-occurrence order: aggr_dev's rule (core/aggr.c:2250-2350,2864-2929) -- NaN for a group without a non-null cell, 0.0 for one
+        cell, else sqrt(max(0, sq/n - (s/n)^2)) (rfx_exec_group_dev).  One shard.  (syncs)"""
+        keys = list(key) if isinstance(key, (list, tuple)) and not (isinstance(key, tuple) and len(key) == 3 and key[0] == "xbar") else [key]
+        c = self._resolve(col, table)
+        q, n = self._query(where, [], table, None, keys, flags)
+        c = self._check_col(c, n)
+        self._keep.append(c)
+        g = L.Groups()
+        self._xcheck(self.lib.rfx_exec_group_by(self._x, C.byref(q), C.byref(g)), "group_by")
+        own = _Owner(self, g, self.lib.rfx_exec_groups_free)
+        ng = int(g.groups)
+        out = torch.empty(ng, dtype=torch.float64, device=self.device)
+        self._xcheck(self.lib.rfx_exec_group_dev(self._x, C.byref(q), C.byref(g), c.data_ptr(), _ctype_of(c), out.data_ptr()), "group_dev")
+        return dict(groups=ng, keys=self._view(own, g.d_keys, ng, torch.int64), dev=out, path=int(g.path))
 
     def _arg_f64(self, col, table) -> bool:
         """Element type of an aggregate's argument: a column, or (op lhs rhs) with the reference's promotion (the library's own rule)."""

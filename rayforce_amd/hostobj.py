@@ -38,7 +38,7 @@ OPS_PROTOTYPES = {
     "rfx_or_sf": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
     "rfx_left_join": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
     "rfx_inner_join": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
-    **{f"rfx_{n}": (C.c_void_p, [C.c_void_p]) for n in ("where", "sum", "avg", "min", "max", "count", "first", "pin", "unpin", "invalidate", "stats", "group", "med", "iasc", "idesc", "asc", "desc", "rank")},
+    **{f"rfx_{n}": (C.c_void_p, [C.c_void_p]) for n in ("where", "sum", "avg", "min", "max", "count", "first", "last", "dev", "pin", "unpin", "invalidate", "stats", "group", "med", "iasc", "idesc", "asc", "desc", "rank")},
     "rfx_xasc": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_xdesc": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_last_sort_on_gpu": (C.c_int, []),
