@@ -281,6 +281,27 @@ int rfx_exec_set_filter(rfx_exec_t *x, const int64_t *d_x, int64_t nx, const int
 /* cells of the reference's table for `len` rows: the first prime >= ceil(len / 0.75) (ht_oa_create, core/hash.c:35-56; host only) */
 int64_t rfx_set_table_cells(int64_t len);
 
+/* ---- bucket verbs (rfx_bucket.hip) ----
+ * rfx_exec_xrank (ray_xrank, core/order.c:598-649): d_out[i] = the bucket in [0, nb) of row i's rank among the n cells of d_col (RFX_I64, also TIMESTAMP, or
+ *   RFX_F64) -- rfx_exec_sort of the one column, ascending, then the fused scatter (rank * nb) / n; scratch 8 B per row beside the sort's, freed before
+ *   return; RFX_ENOMEM when it does not fit (the operator layer hands the verb to the host).  attrs: RFX_XRANK_ASC / RFX_XRANK_DESC say the column
+ *   carries that attribute: the index formula alone runs and d_col is not read.  One shard only (RFX_ELIMIT "xrank over a sharded table").  nb > 0 and
+ *   (n - 1) * nb < 2^63; n = 0 answers nothing without dividing.
+ * rfx_exec_xbar / _round / _neg / _within: rfx_hip_xbar / rfx_hip_round_f64 / rfx_hip_neg / rfx_hip_within_i64 over every shard's rows.  The operands are
+ *   given per shard: d_xs[s] is shard s's piece (rows rfx_exec_split(n, S, s)); a NULL array is an atom (xbar).  shard < 0: all shards, n the whole
+ *   length, returns with the shards' streams idle when there is more than one; shard >= 0: that shard's piece alone, n ITS rows, enqueued on its
+ *   context (the operator layer's pieces).  RFX_XSTAT_XRANKS / _XRANK_SORTED / _BUCKET_MAPS count what ran. */
+enum { RFX_XRANK_ASC = 2, RFX_XRANK_DESC = 4 }; /* (the reference's ATTR_ASC / ATTR_DESC bits) */
+int rfx_exec_xrank(rfx_exec_t *x, const void *d_col, int32_t type, int attrs, int64_t n, int64_t nb, int64_t *d_out);
+/* which arm of ray_xbar_partial (core/math.c:1635-1782) a pair of operand types takes: x_type / y_type are the reference's type codes without the atom's
+ * sign (I32 4, I64 5, DATE 7, TIME 8, TIMESTAMP 9, F64 10); fills desc's x_type, y_type, mid, y_time and out_bytes, *out_type = the result's type code
+ * (infer_xbar_type).  RFX_EINVAL: the reference has no such arm (its type error). */
+int rfx_exec_xbar_plan(int x_type, int y_type, rfx_xbar_desc_t *desc, int *out_type);
+int rfx_exec_xbar(rfx_exec_t *x, const rfx_xbar_desc_t *desc, const void *const *d_xs, const void *const *d_ys, int64_t n, void *const *d_outs, int shard);
+int rfx_exec_round(rfx_exec_t *x, int op, const void *const *d_ins, int64_t n, void *const *d_outs, int shard);
+int rfx_exec_neg(rfx_exec_t *x, int32_t type, const void *const *d_ins, int64_t n, void *const *d_outs, int shard);
+int rfx_exec_within(rfx_exec_t *x, const void *const *d_cols, int64_t lo, int64_t hi, int64_t n, void *const *d_masks, int shard);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -317,7 +338,10 @@ enum {
     RFX_XSTAT_SET_FILTERS = 25,   /* sect / except calls */
     RFX_XSTAT_NS_SET_BUILD = 26,  /* wall time of the set verbs' scope + build halves, nanoseconds, to the stream idle */
     RFX_XSTAT_NS_SET_PROBE = 27,  /* ... and of their probe / emit halves */
-    RFX_XSTAT_N = 28
+    RFX_XSTAT_XRANKS = 28,        /* xrank calls answered by the device path */
+    RFX_XSTAT_XRANK_SORTED = 29,  /* ... of which an ASC / DESC attribute answered without a sort */
+    RFX_XSTAT_BUCKET_MAPS = 30,   /* element-wise bucket maps run: xbar, floor / ceil / round, neg, within (one per call or operator piece) */
+    RFX_XSTAT_N = 31
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

@@ -755,6 +755,45 @@ int rfx_hip_set_cells_flags(rfx_ctx_t *ctx, const int64_t *d_cells, int64_t P, u
 int rfx_hip_set_compact(rfx_ctx_t *ctx, const uint64_t *d_flags, int64_t nbits, int mode, int64_t kmin, const int64_t *d_src, const int64_t *d_a, int64_t na,
                         const int64_t *d_b, int64_t *d_scan, int64_t cap, int64_t *d_out, int64_t *count);
 
+/* ---- bucket verbs (rfx_bucket.hip): xrank, xbar, floor / ceil / round, neg, within as columns of their own ----
+ * rfx_hip_xrank: d_out[d_perm[r]] = (r * nb) / n for r < n (xrank_worker, core/order.c:589-596) -- rfx_hip_inverse_perm's scatter with the bucket of
+ *   the rank fused in; entries of d_perm outside [0, n) are ignored.  nb > 0 and (n - 1) * nb < 2^63.
+ * rfx_hip_xrank_sorted: the attribute short-cuts (xrank_asc_worker / xrank_desc_worker, :564-580): d_out[i] = (idx * nb) / n with idx = i, or
+ *   n - 1 - i when descending.  No sort, no read.
+ * rfx_hip_xbar: ray_xbar_partial's vector arms (core/math.c:1635-1782) cell for cell: out = mid_to_out(XBAR<mid>(x_to_mid(x), y_to_mid(y))),
+ *   XBARI32 / XBARI64 / XBARF64 of core/ops.h:190-197.  An operand is a device column (d_x / d_y) or an atom (NULL pointer, bits in x_atom / y_atom
+ *   in the operand's own element type, a 4-byte atom in the low half).  x_type / y_type: RFX_I32 | RFX_I64 | RFX_F64 (the element's storage; DATE /
+ *   TIME are RFX_I32, TIMESTAMP RFX_I64).  mid: the type the formula runs in; the promotions are the reference's (i32_to_i64, i32_to_f64, i64_to_f64:
+ *   null -> null; y_time = 1: y is a TIME cell under a TIMESTAMP x, time_to_timestamp: null -> null, else x 10^6).  out_bytes 4 | 8: an I64 result
+ *   stored into 4 bytes narrows as i64_to_date / i64_to_time (null -> NULL_I32, else truncation).  The f64 middle type computes as the reference's
+ *   build does: subnormals are zeros, an ATOM divisor is divided by through its reciprocal, a null quotient answers the canonical NaN and 0 * inf
+ *   x86's default NaN (sign bit set).
+ *   Columns and d_out 16-byte aligned.
+ * rfx_hip_round_f64: FLOORF64 / CEILF64 / ROUNDF64 (core/ops.h:190-192) with their (i64) cast as x86 converts: a NaN, an infinity or |x| >= 2^63
+ *   converts to INT64_MIN; a subnormal cell is a zero of its sign.  d_out may be d_in.
+ * rfx_hip_neg: ray_neg's vector arms (core/order.c:474-492): RFX_I32 -> i64 cells -(i64)x (a NULL_I32 gives 2^31; RFX_I32_WIDE: the
+ *   same cells held as their widened 8-byte image, rfx_hip_widen_i32, the null's promotion undone; d_out may then be d_in), RFX_I64 -> wrapping -x (a null
+ *   stays the null), RFX_F64 -> the sign bit flipped (NaNs too).
+ * rfx_hip_within_i64: d_mask[i] = lo <= d_col[i] && d_col[i] <= hi as 0 / 1 bytes (ray_within, core/items.c:863-872: plain signed compares, a null
+ *   cell is the smallest value); d_col 16-byte, d_mask 8-byte aligned. */
+enum { RFX_I32 = 4, RFX_I32_WIDE = 0x104 }; /* (_WIDE: rfx_hip_neg alone) */
+enum { RFX_ROUND_FLOOR = 0, RFX_ROUND_CEIL = 1, RFX_ROUND_ROUND = 2 };
+typedef struct rfx_xbar_desc {
+    const void *d_x, *d_y;
+    uint64_t x_atom, y_atom;
+    int32_t x_type, y_type;
+    int32_t mid;
+    int32_t y_time;
+    int32_t out_bytes;
+    int32_t widened; /* bit 0 / 1: x / y is RFX_I32 held as 8-byte cells (rfx_hip_widen_i32: what the operator layer's resident copies are) */
+} rfx_xbar_desc_t;
+int rfx_hip_xrank(rfx_ctx_t *ctx, const int64_t *d_perm, int64_t n, int64_t nb, int64_t *d_out);
+int rfx_hip_xrank_sorted(rfx_ctx_t *ctx, int64_t n, int64_t nb, int descending, int64_t *d_out);
+int rfx_hip_xbar(rfx_ctx_t *ctx, const rfx_xbar_desc_t *desc, int64_t n, void *d_out);
+int rfx_hip_round_f64(rfx_ctx_t *ctx, int op, const double *d_in, int64_t n, double *d_out);
+int rfx_hip_neg(rfx_ctx_t *ctx, int32_t type, const void *d_in, int64_t n, void *d_out);
+int rfx_hip_within_i64(rfx_ctx_t *ctx, const int64_t *d_col, int64_t lo, int64_t hi, int64_t n, int8_t *d_mask);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

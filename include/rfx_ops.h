@@ -214,6 +214,29 @@ int rfx_last_set_route(void);
  * rfx_stats, whose 17 cells stay what they were: what tells a host that the device answered. */
 rfx_obj_p rfx_set_stats(rfx_obj_p ignored);
 
+/* The bucket verbs as built-ins of their own (rfx_bucket.hip), every result a fresh host vector of the reference's result type:
+ *   binary_f (xrank v n)  ray_xrank  core/order.c:598-649   v an I64 / TIMESTAMP / F64 vector (host vector or device-column handle), n an atom of type
+ *       -I64 / -I32 / -I16 / -U8: I64 of v's length, cell i = (rank of v[i] under the stable ascending sort * n) / len; a v carrying ATTR_ASC /
+ *       ATTR_DESC is answered from the attribute by the index formula alone; an empty v answers I64[0] without dividing.
+ *   binary_f (xbar x y)   ray_xbar   core/math.c:1635-1782  every arm of ray_xbar_partial with at least one vector operand: x of I32 / I64 / F64 / DATE /
+ *       TIME / TIMESTAMP, y an atom or vector of the types that arm lists (atom x with vector y included) -> I32 / I64 / F64 / DATE / TIME / TIMESTAMP
+ *       by infer_xbar_type.  The function object behind "xbar" inside by: is still bucketed by rfx_select's planner as before.
+ *   binary_f (within x r) ray_within core/items.c:848-872   an I64 vector against a 2-cell I64 vector -> B8
+ *   unary_f  floor / ceil / round    core/math.c:2047-2117  F64 vectors -> F64, the reference's FLOORF64 / CEILF64 / ROUNDF64 with their (i64) casts
+ *   unary_f  neg          ray_neg    core/order.c:445-497   I32 / I64 vectors -> I64, F64 -> F64
+ * The host's own verb answers every other shape -- atoms alone, other vector types, n <= 0 or of another type (xrank's domain / type errors), (len - 1) * n
+ * beyond 63 bits, vectors of unequal length, xrank over sharded columns or without room for its scratch -- and every error it words itself; without a
+ * host those are refused with the reason, which is also in rfx_ops_last_error().  The element-wise verbs run over every shard's rows. */
+rfx_obj_p rfx_xrank(rfx_obj_p v, rfx_obj_p n);
+rfx_obj_p rfx_xbar(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_within(rfx_obj_p x, rfx_obj_p range);
+rfx_obj_p rfx_floor(rfx_obj_p x);
+rfx_obj_p rfx_ceil(rfx_obj_p x);
+rfx_obj_p rfx_round(rfx_obj_p x);
+rfx_obj_p rfx_neg(rfx_obj_p x);
+/* 1: the last of those seven calls was answered by the device path (an empty vector included: no launch); 0: it went to the host or failed */
+int rfx_last_bucket_on_gpu(void);
+
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns
  * carry the mapping's values at the selected rows (value i at row ids[i]; under by: every group's aggregate at all of its selected

@@ -8,6 +8,8 @@ RFX_OK = 0
 RFX_ELIMIT = -5
 RFX_ESTATE = -6
 RFX_B8, RFX_I64, RFX_F64 = 1, 5, 10
+RFX_I32 = 4  # element storage of the bucket verbs' 4-byte operands (I32 / DATE / TIME)
+RFX_ROUND_FLOOR, RFX_ROUND_CEIL, RFX_ROUND_ROUND = 0, 1, 2
 RFX_EQ, RFX_NE, RFX_LT, RFX_GT, RFX_LE, RFX_GE = range(6)
 RFX_AND, RFX_OR = 0, 1
 RFX_AGG_SUM, RFX_AGG_MIN, RFX_AGG_MAX, RFX_AGG_COUNT, RFX_AGG_AVG, RFX_AGG_FIRST, RFX_AGG_LAST = range(7)
@@ -106,11 +108,17 @@ class HashTables(C.Structure):
                 ("d_first", C.c_void_p), ("d_acc", C.c_void_p * RFX_MAX_AGGS), ("d_cnt", C.c_void_p * RFX_MAX_AGGS)]
 
 
+class XbarDesc(C.Structure):  # rfx_xbar_desc_t
+    _fields_ = [("d_x", C.c_void_p), ("d_y", C.c_void_p), ("x_atom", C.c_uint64), ("y_atom", C.c_uint64), ("x_type", C.c_int32), ("y_type", C.c_int32),
+                ("mid", C.c_int32), ("y_time", C.c_int32), ("out_bytes", C.c_int32), ("widened", C.c_int32)]
+
+
 class SetLookup(C.Structure):  # rfx_set_lookup_t
     _fields_ = [("kind", C.c_int32), ("null_hit", C.c_int32), ("kmin", C.c_int64), ("range", C.c_int64), ("d_bits", C.c_void_p), ("d_first", C.c_void_p),
                 ("d_keys", C.c_void_p), ("capacity", C.c_int64), ("atom", C.c_int64)]
 
 
+assert C.sizeof(XbarDesc) == 56
 assert C.sizeof(Pred) == 40 and C.sizeof(Agg) == 56 and C.sizeof(XNode) == 56 and C.sizeof(Partial) == 64 and C.sizeof(Value) == 16
 
 # ---- include/rfx_exec.h: the planner's structures ----
@@ -125,6 +133,8 @@ RFX_XSTAT_SCOPE_SAMPLED, RFX_XSTAT_SCOPE_RETRIED, RFX_XSTAT_SCOPE_REMEMBERED, RF
 RFX_XSTAT_SORTS, RFX_XSTAT_SORT_PASSES = 16, 17
 RFX_XSTAT_ASOF_JOINS, RFX_XSTAT_BINS, RFX_XSTAT_SEARCHES, RFX_XSTAT_NS_ASOF_BUILD, RFX_XSTAT_NS_ASOF_PROBE = 18, 19, 20, 21, 22
 RFX_XSTAT_SET_DISTINCTS, RFX_XSTAT_SET_MEMBERS, RFX_XSTAT_SET_FILTERS, RFX_XSTAT_NS_SET_BUILD, RFX_XSTAT_NS_SET_PROBE = 23, 24, 25, 26, 27
+RFX_XSTAT_XRANKS, RFX_XSTAT_XRANK_SORTED, RFX_XSTAT_BUCKET_MAPS = 28, 29, 30
+RFX_XRANK_ASC, RFX_XRANK_DESC = 2, 4
 RFX_SET_ROUTE_UNDEFINED, RFX_SET_ROUTE_NONE, RFX_SET_ROUTE_DENSE, RFX_SET_ROUTE_HASH, RFX_SET_ROUTE_DISJOINT, RFX_SET_ROUTE_ATOM = -1, 0, 1, 2, 3, 4
 RFX_WAGG = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "first": 5, "last": 6}  # include/rfx_hip.h RFX_WAGG_*
 RFX_XSTAT_PHASES = (("scope", 9), ("pass", 10), ("merge", 11), ("rank", 12), ("emit", 13), ("fetch", 14), ("total", 15))
@@ -288,6 +298,12 @@ PROTOTYPES = {
     "rfx_hip_sort_index": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "rfx_hip_sort_values": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "rfx_hip_inverse_perm": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_xrank": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_xrank_sorted": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    "rfx_hip_xbar": (C.c_int, [_ctx, _P(XbarDesc), C.c_int64, C.c_void_p]),
+    "rfx_hip_round_f64": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_neg": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_within_i64": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_set_scope": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_int64)]),
@@ -363,6 +379,12 @@ EXEC_PROTOTYPES = {
     "rfx_exec_group_dev": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rfx_exec_sort": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_exec_sort_values": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rfx_exec_xrank": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_exec_xbar_plan": (C.c_int, [C.c_int, C.c_int, _P(XbarDesc), _P(C.c_int)]),
+    "rfx_exec_xbar": (C.c_int, [_exec, _P(XbarDesc), _P(C.c_void_p), _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
+    "rfx_exec_round": (C.c_int, [_exec, C.c_int, _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
+    "rfx_exec_neg": (C.c_int, [_exec, C.c_int32, _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
+    "rfx_exec_within": (C.c_int, [_exec, _P(C.c_void_p), C.c_int64, C.c_int64, C.c_int64, _P(C.c_void_p), C.c_int]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_bin": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,

@@ -258,6 +258,56 @@ __device__ __forceinline__ u64 rfx_expr_eval(int op, int out_f64, int l_f64, int
     return rfx_as_u64(r);
 }
 
+// XBARI64 / XBARI32 -- core/ops.h:193-196: y == 0 or a null operand -> null, else ((x < 0 ? x + 1 - y : x) / y) * y; C division truncates towards
+// zero, hence the shift for negative x.  The adjustment and the product wrap like the reference's build.  (by: keys and the xbar verb share these.)
+__device__ __forceinline__ i64 rfx_xbar_i64(i64 x, i64 y) {
+    if (y == 0 || x == RFX_NULL_I64_D || y == RFX_NULL_I64_D) return RFX_NULL_I64_D;
+    const i64 a = (x < 0) ? (i64)((u64)x + 1u - (u64)y) : x;
+    if (y == -1) return a; // ((a / -1) * -1, without the one quotient that does not exist)
+    return (i64)((u64)(a / y) * (u64)y);
+}
+#define RFX_NULL_I32_D ((int)0x80000000)
+__device__ __forceinline__ int rfx_xbar_i32(int x, int y) {
+    if (y == 0 || x == RFX_NULL_I32_D || y == RFX_NULL_I32_D) return RFX_NULL_I32_D;
+    const int a = (x < 0) ? (int)((unsigned)x + 1u - (unsigned)y) : x;
+    if (y == -1) return a;
+    return (int)((unsigned)(a / y) * (unsigned)y);
+}
+// (i64_t)x as x86 converts it (cvttsd2si): a NaN, an infinity or a value outside [-2^63, 2^63) gives INT64_MIN
+__device__ __forceinline__ i64 rfx_f64_to_i64_x86(double x) {
+    return (x >= -9223372036854775808.0 && x < 9223372036854775808.0) ? (i64)x : RFX_NULL_I64_D;
+}
+// The reference's build computes f64 with denormals-are-zero and flush-to-zero set (its unsafe-math link sets MXCSR so): a subnormal operand or result
+// is a signed zero there.  The device keeps subnormals, so the cells that meet one are flushed by hand.
+__device__ __host__ __forceinline__ u64 rfx_ftz_bits(u64 b) { return (b & 0x7FF0000000000000ULL) == 0 ? (b & 0x8000000000000000ULL) : b; }
+// FLOORF64 / CEILF64 / ROUNDF64 -- core/ops.h:190-192, on bits: NaN -> the null; the arms are the reference's expressions with their (i64_t) casts
+__device__ __forceinline__ u64 rfx_floor_f64_bits(u64 b) {
+    if (rfx_isnan_bits(b)) return RFX_NAN_BITS;
+    const double x = rfx_as_f64(rfx_ftz_bits(b));
+    const i64 t = rfx_f64_to_i64_x86(x);
+    return rfx_as_u64((x < 0.0 && (double)t != x) ? (double)t - 1.0 : (double)t);
+}
+__device__ __forceinline__ u64 rfx_ceil_f64_bits(u64 b) {
+    if (rfx_isnan_bits(b)) return RFX_NAN_BITS;
+    return rfx_floor_f64_bits(b ^ 0x8000000000000000ULL) ^ 0x8000000000000000ULL; // -FLOORF64(-x)
+}
+__device__ __forceinline__ u64 rfx_round_f64_bits(u64 b) {
+    if (rfx_isnan_bits(b)) return RFX_NAN_BITS;
+    const double x = rfx_as_f64(rfx_ftz_bits(b));
+    return rfx_as_u64((double)(x >= 0.0 ? rfx_f64_to_i64_x86(x + 0.5) : rfx_f64_to_i64_x86(x - 0.5)));
+}
+// XBARF64 -- core/ops.h:197: FLOORF64(x / y) * y as the reference's build computes it (tests/golden/bucket_golden.npz): a loop-invariant divisor (an
+// atom y) is divided by through its reciprocal (reciprocal-math: rb = 1 / y once, flushed; the quotient is x * r), a vector divisor by a division.
+// A null quotient stays the null through the product; a NaN the product itself makes (0 * inf) is x86's default NaN, the sign bit set.
+__device__ __forceinline__ u64 rfx_xbar_f64_bits(u64 xb, u64 yb, u64 rb, bool recip) {
+    xb = rfx_ftz_bits(xb);
+    yb = rfx_ftz_bits(yb);
+    const u64 q = rfx_ftz_bits(rfx_as_u64(recip ? rfx_as_f64(xb) * rfx_as_f64(rb) : rfx_as_f64(xb) / rfx_as_f64(yb)));
+    const u64 f = rfx_floor_f64_bits(q);
+    const u64 r = rfx_ftz_bits(rfx_as_u64(rfx_as_f64(f) * rfx_as_f64(yb)));
+    if (rfx_isnan_bits(r)) return rfx_isnan_bits(f) ? RFX_NAN_BITS : 0xFFF8000000000000ULL;
+    return r;
+}
 // {EQ,NE,LT,GT,LE,GE}I64 -- core/ops.h:80,88,96,104,112,120 : plain signed compares, no null test
 __device__ __forceinline__ bool rfx_cmp_i64(int op, i64 x, i64 y) {
     switch (op) {
@@ -320,4 +370,23 @@ __device__ __forceinline__ u64x2 rfx_ld2(const u64 *p) {
     v2 t = __builtin_nontemporal_load((const v2 *)p);
     u64x2 r; r.x = t.x; r.y = t.y;
     return r;
+}
+
+// B8 masks leave TRANSPOSED (k_cmp_mask, rfx_scalar.hip): a wave holds 512 consecutive rows, lane l rows 2l, 2l + 1 of each of four 128-row groups, bit
+// 2j / 2j + 1 of m the verdicts of group j's even / odd row.  The eight ballots are wave-uniform words; lane l picks the two that hold rows 8l .. 8l + 7
+// (group l / 16), spreads four bits of each into bytes and stores 8 bytes -- 512 contiguous bytes per wave instruction, non-temporal.
+__device__ __forceinline__ void rfx_mask_store512(unsigned m, int lane, int8_t *out512) {
+    u64 be = 0, bo = 0; // ballots of the even / odd rows of this lane's OUTPUT group (lane / 16)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const u64 b0 = __ballot((m >> (2 * j)) & 1u), b1 = __ballot((m >> (2 * j + 1)) & 1u);
+        const bool mine = (lane >> 4) == j;
+        be = mine ? b0 : be;
+        bo = mine ? b1 : bo;
+    }
+    const unsigned sh = 4u * ((unsigned)lane & 15u);
+    const unsigned x0 = (unsigned)(be >> sh) & 15u, x1 = (unsigned)(bo >> sh) & 15u; // rows 8l, 8l+2, 8l+4, 8l+6 / 8l+1, ...
+    const unsigned lo = (x0 & 1u) | ((x1 & 1u) << 8) | (((x0 >> 1) & 1u) << 16) | (((x1 >> 1) & 1u) << 24);
+    const unsigned hi = ((x0 >> 2) & 1u) | (((x1 >> 2) & 1u) << 8) | (((x0 >> 3) & 1u) << 16) | (((x1 >> 3) & 1u) << 24);
+    __builtin_nontemporal_store(((u64)hi << 32) | lo, (u64 *)(out512 + lane * 8));
 }

@@ -90,3 +90,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_asof.c"
 #include "rfx_exec_window.c"
 #include "rfx_exec_set.c"
+#include "rfx_exec_bucket.c"

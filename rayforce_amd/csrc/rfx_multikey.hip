@@ -140,21 +140,18 @@ extern "C" int rfx_hip_composite_decode(rfx_ctx_t *c, const int64_t *d_comp, int
 }
 
 // ---- time / value bucketing as a group key: (xbar col width), XBARI64 core/ops.h:192-193, ray_xbar_partial core/math.c:1635 ----
-// out = null when x is null, else ((x < 0 ? x + 1 - w : x) / w) * w -- floor to a multiple of w for w > 0 (C division truncates
-// towards zero, hence the shift for negative x).  Only w > 0 is taken here; the adjustment wraps like the reference's.
+// rfx_xbar_i64 (rfx_common.hpp): floor to a multiple of w for w > 0.  Only w > 0 is taken here.
 __global__ __launch_bounds__(RFX_BLOCK) void k_xbar_i64(const u64 *__restrict__ in, i64 nrows, i64 w, u64 *__restrict__ out) {
     const i64 npairs = nrows / 2;
     for (i64 i = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x; i < npairs; i += (i64)gridDim.x * RFX_BLOCK) {
         const u64x2 t = rfx_ld2(in + 2 * i);
         u64x2 o;
-        const i64 x0 = (i64)t.x, x1 = (i64)t.y;
-        o.x = (x0 == RFX_NULL_I64_D) ? t.x : (u64)(((x0 < 0) ? (i64)((u64)x0 + 1u - (u64)w) : x0) / w * w);
-        o.y = (x1 == RFX_NULL_I64_D) ? t.y : (u64)(((x1 < 0) ? (i64)((u64)x1 + 1u - (u64)w) : x1) / w * w);
+        o.x = (u64)rfx_xbar_i64((i64)t.x, w);
+        o.y = (u64)rfx_xbar_i64((i64)t.y, w);
         *(u64x2 *)(out + 2 * i) = o;
     }
     if ((nrows & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const i64 x = (i64)in[nrows - 1];
-        out[nrows - 1] = (x == RFX_NULL_I64_D) ? (u64)x : (u64)(((x < 0) ? (i64)((u64)x + 1u - (u64)w) : x) / w * w);
+        out[nrows - 1] = (u64)rfx_xbar_i64((i64)in[nrows - 1], w);
     }
 }
 

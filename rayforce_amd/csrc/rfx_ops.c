@@ -55,16 +55,16 @@ static struct {
  * The ids after F_BINR lie outside the range: window_agg (rfx_ops_window.c) recognises F_LAST and refuses F_DEV; F_DISTINCT .. F_UNION (and F_IN as a
  * verb of its own) are the set verbs of rfx_ops_set.c, which no reader of fn_id maps -- inside where: F_IN stays the comparison list of
  * rfx_ops_plan.c and nothing else. */
-enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_DEV, F_N };
+enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_DEV, F_XRANK, F_FLOOR, F_CEIL, F_ROUND, F_NEG, F_N };
 static const char *HOST_FN[F_N] = {"ray_sum", "ray_avg", "ray_min", "ray_max", "ray_count", "ray_first", "ray_eq",  "ray_ne",  "ray_lt",  "ray_gt",
                                    "ray_le",  "ray_ge",  "ray_and", "ray_or",  "ray_select", "ray_add",  "ray_sub", "ray_mul", "ray_fdiv", "ray_div", "ray_mod", "ray_xbar",
                                    "ray_left_join", "ray_inner_join", "ray_update", "ray_take", "ray_in", "ray_within", "ray_not", "ray_med",
                                    "ray_iasc", "ray_idesc", "ray_asc", "ray_desc", "ray_rank", "ray_xasc", "ray_xdesc",
                                    "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last",
-                                   "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union", "ray_dev"}; /* (in / within / not: recognised inside where: only) */
-/* xbar is recognised inside `by:` only; the standalone object model still needs a distinct function object for it:
- * this stub is never called by this library. */
-static obj_p x_stub_xbar(obj_p a, obj_p b) { (void)a; (void)b; return NULL; }
+                                   "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union", "ray_dev",
+                                   "ray_xrank", "ray_floor", "ray_ceil", "ray_round", "ray_neg"}; /* (not: recognised inside where: only; in / within also verbs of their own) */
+/* xbar inside `by:` is recognised by its function object (fn_id -> F_XBAR) and bucketed by the planner; called as a verb it is rfx_xbar
+ * (rfx_ops_bucket.c), which the standalone object model binds to "xbar". */
 static void *OUR_FN[F_N];
 static void *g_host_where, *g_host_at, *g_host_group; /* the host's built-ins behind rfx_where / rfx_at / rfx_group (NULL without a host) */
 static char g_err[640];
@@ -80,7 +80,8 @@ int rfx_host_bind(void) {
     OUR_FN[F_LT] = (void *)rfx_lt; OUR_FN[F_GT] = (void *)rfx_gt; OUR_FN[F_LE] = (void *)rfx_le; OUR_FN[F_GE] = (void *)rfx_ge;
     OUR_FN[F_AND] = (void *)rfx_and; OUR_FN[F_OR] = (void *)rfx_or; OUR_FN[F_SELECT] = (void *)rfx_select;
     OUR_FN[F_ADD] = (void *)rfx_add; OUR_FN[F_SUB] = (void *)rfx_sub; OUR_FN[F_MUL] = (void *)rfx_mul; OUR_FN[F_FDIV] = (void *)rfx_div; OUR_FN[F_DIV] = (void *)rfx_floordiv; OUR_FN[F_MOD] = (void *)rfx_mod;
-    OUR_FN[F_XBAR] = (void *)x_stub_xbar;
+    OUR_FN[F_XBAR] = (void *)rfx_xbar; OUR_FN[F_WITHIN] = (void *)rfx_within; OUR_FN[F_XRANK] = (void *)rfx_xrank;
+    OUR_FN[F_FLOOR] = (void *)rfx_floor; OUR_FN[F_CEIL] = (void *)rfx_ceil; OUR_FN[F_ROUND] = (void *)rfx_round; OUR_FN[F_NEG] = (void *)rfx_neg;
     OUR_FN[F_LJ] = (void *)rfx_left_join; OUR_FN[F_IJ] = (void *)rfx_inner_join; OUR_FN[F_UPDATE] = (void *)rfx_update;
     OUR_FN[F_MED] = (void *)rfx_med; /* (not inside the F_SUM..F_FIRST range the select / update mappings check: select takes it by name) */
     OUR_FN[F_IASC] = (void *)rfx_iasc; OUR_FN[F_IDESC] = (void *)rfx_idesc; OUR_FN[F_ASC] = (void *)rfx_asc; OUR_FN[F_DESC] = (void *)rfx_desc;
@@ -144,7 +145,9 @@ obj_p rfx_host_fn(const char *name) {
         {"asof-join", F_AJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"bin", F_BIN, RFX_TYPE_BINARY, RFX_FN_NONE}, {"binr", F_BINR, RFX_TYPE_BINARY, RFX_FN_NONE},
         {"window-join", F_WJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"window-join1", F_WJ1, RFX_TYPE_VARY, RFX_FN_NONE}, {"last", F_LAST, RFX_TYPE_UNARY, RFX_FN_AGGR},
         {"distinct", F_DISTINCT, RFX_TYPE_UNARY, RFX_FN_NONE}, {"find", F_FIND, RFX_TYPE_BINARY, RFX_FN_NONE}, {"in", F_IN, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"sect", F_SECT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"except", F_EXCEPT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"union", F_UNION, RFX_TYPE_BINARY, RFX_FN_NONE}};
+        {"sect", F_SECT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"except", F_EXCEPT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"union", F_UNION, RFX_TYPE_BINARY, RFX_FN_NONE},
+        {"xrank", F_XRANK, RFX_TYPE_BINARY, RFX_FN_NONE}, {"floor", F_FLOOR, RFX_TYPE_UNARY, RFX_FN_ATOMIC}, {"ceil", F_CEIL, RFX_TYPE_UNARY, RFX_FN_ATOMIC},
+        {"round", F_ROUND, RFX_TYPE_UNARY, RFX_FN_ATOMIC}, {"neg", F_NEG, RFX_TYPE_UNARY, RFX_FN_ATOMIC}};
     rfx_host_bind();
     for (size_t i = 0; i < sizeof(T) / sizeof(T[0]); i++)
         if (strcmp(T[i].n, name) == 0) {
@@ -201,3 +204,4 @@ static int fn_id(obj_p o) {
 #include "rfx_ops_asof.c"
 #include "rfx_ops_window.c"
 #include "rfx_ops_set.c"
+#include "rfx_ops_bucket.c"

@@ -446,19 +446,7 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_cmp_mask(const Plan P, int8_t *__
             }
         }
         const unsigned m = eval_preds<NC, 8, 1>(S, v, 0xffu);
-        u64 be = 0, bo = 0; // ballots of the even / odd rows of this lane's OUTPUT group (lane / 16)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const u64 b0 = __ballot((m >> (2 * j)) & 1u), b1 = __ballot((m >> (2 * j + 1)) & 1u);
-            const bool mine = (lane >> 4) == j;
-            be = mine ? b0 : be;
-            bo = mine ? b1 : bo;
-        }
-        const unsigned sh = 4u * ((unsigned)lane & 15u);
-        const unsigned x0 = (unsigned)(be >> sh) & 15u, x1 = (unsigned)(bo >> sh) & 15u; // rows 8l, 8l+2, 8l+4, 8l+6 / 8l+1, ...
-        const unsigned lo = (x0 & 1u) | ((x1 & 1u) << 8) | (((x0 >> 1) & 1u) << 16) | (((x1 >> 1) & 1u) << 24);
-        const unsigned hi = ((x0 >> 2) & 1u) | (((x1 >> 2) & 1u) << 8) | (((x0 >> 3) & 1u) << 16) | (((x1 >> 3) & 1u) << 24);
-        __builtin_nontemporal_store(((u64)hi << 32) | lo, (u64 *)(out + q * 512 + lane * 8));
+        rfx_mask_store512(m, lane, out + q * 512);
     }
     // tail rows
     if (blockIdx.x == 0) {

@@ -374,6 +374,109 @@ class Engine:
         self._xcheck(self.lib.rfx_exec_sort_values(self._x, col.data_ptr(), _ctype_of(col), int(bool(descending)), col.numel(), out.data_ptr(), None), "sort")
         return out
 
+    # ------------------------------------------------------------------ bucket verbs (rfx_bucket.hip through rfx_exec_bucket.c)
+    _BK_TYPES = {"i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}  # the reference's type codes
+    _BK_DTYPE = {4: torch.int32, 7: torch.int32, 8: torch.int32, 5: torch.int64, 9: torch.int64, 10: torch.float64}
+
+    def _pieces(self, t: torch.Tensor):
+        """Per shard the address of its rows (rfx_exec_split) of a whole device tensor."""
+        out = (C.c_void_p * L.RFX_MAX_SHARDS)()
+        for s in range(self.shards):
+            r0 = C.c_int64()
+            self.lib.rfx_exec_split(t.numel(), self.shards, s, C.byref(r0), None)
+            out[s] = t.data_ptr() + r0.value * t.element_size()
+        return out
+
+    def _operands_written(self):
+        """Before an element-wise map over more than one shard: shards 1.. run on streams of their own, which do not wait for torch's stream, so what
+        torch enqueued there -- the kernels that made the operands -- has to have finished (as in _query)."""
+        if self.shards > 1:
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def xrank(self, col: torch.Tensor, n: int, attr: Optional[str] = None) -> torch.Tensor:
+        """(xrank col n): per cell the bucket in [0, n) of its rank under the stable ascending sort, (rank * n) // len (rfx_exec_xrank).  ``attr`` =
+        "asc" / "desc": the column carries that attribute, the index formula alone runs.  One shard."""
+        self._check_col(col)
+        out = torch.empty(col.numel(), dtype=torch.int64, device=self.device)
+        attrs = {None: 0, "asc": L.RFX_XRANK_ASC, "desc": L.RFX_XRANK_DESC}[attr]
+        self._xcheck(self.lib.rfx_exec_xrank(self._x, col.data_ptr(), _ctype_of(col), attrs, col.numel(), int(n), out.data_ptr()), "xrank")
+        return out
+
+    def xbar(self, x, y, xtype: Optional[str] = None, ytype: Optional[str] = None) -> torch.Tensor:
+        """(xbar x y), ray_xbar_partial's arms: an operand is a device column (int32 / int64 / float64) or a Python atom; ``xtype`` / ``ytype`` name
+        the reference's type where the dtype does not ("date", "time", "timestamp"; an int atom is "i64", or "i32" / "time" ... when said so)."""
+        import struct
+        d = L.XbarDesc()
+        codes, tens = [], []
+        for v, name in ((x, xtype), (y, ytype)):
+            if isinstance(v, torch.Tensor):
+                self._check_col(v)
+                code = self._BK_TYPES[name] if name else {torch.int32: 4, torch.int64: 5, torch.float64: 10}.get(v.dtype)
+                if code is None or self._BK_DTYPE[code] != v.dtype:
+                    raise RfxError(f"xbar: a {v.dtype} column cannot be {name or 'an operand'}")
+                tens.append(v)
+            else:
+                code = self._BK_TYPES[name] if name else (10 if isinstance(v, float) else 5)
+                tens.append(None)
+            codes.append(code)
+        if tens[0] is None and tens[1] is None:
+            raise RfxError("xbar: at least one operand is a column")
+        if tens[0] is not None and tens[1] is not None and tens[0].numel() != tens[1].numel():
+            raise RfxError("length")
+        ot = C.c_int()
+        if self.lib.rfx_exec_xbar_plan(codes[0], codes[1], C.byref(d), C.byref(ot)) != L.RFX_OK:
+            raise RfxError(f"xbar: the reference has no arm for the types {codes[0]} and {codes[1]}")
+        bits = []
+        for v, code in zip((x, y), codes):
+            if isinstance(v, torch.Tensor):
+                bits.append(0)
+            elif code == 10:
+                bits.append(struct.unpack("<Q", struct.pack("<d", float(v)))[0])
+            else:
+                bits.append(int(v) & (0xFFFFFFFF if self._BK_DTYPE[code] == torch.int32 else 0xFFFFFFFFFFFFFFFF))
+        d.x_atom, d.y_atom = bits
+        n = (tens[0] if tens[0] is not None else tens[1]).numel()
+        out = torch.empty(n, dtype=self._BK_DTYPE[ot.value], device=self.device)
+        xs = self._pieces(tens[0]) if tens[0] is not None else None
+        ys = self._pieces(tens[1]) if tens[1] is not None else None
+        self._operands_written()
+        self._xcheck(self.lib.rfx_exec_xbar(self._x, C.byref(d), xs, ys, n, self._pieces(out), -1), "xbar")
+        return out
+
+    def within(self, col: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
+        """(within col [lo hi]) over an i64 column: a B8 mask (int8 tensor of 0 / 1), lo <= x <= hi as plain signed compares."""
+        self._check_col(col)
+        if col.dtype != torch.int64:
+            raise RfxError("within: an i64 column is expected")
+        out = torch.empty(col.numel(), dtype=torch.int8, device=self.device)
+        self._operands_written()
+        self._xcheck(self.lib.rfx_exec_within(self._x, self._pieces(col), int(lo), int(hi), col.numel(), self._pieces(out), -1), "within")
+        return out
+
+    def _round(self, op: int, col: torch.Tensor, what: str) -> torch.Tensor:
+        self._check_col(col)
+        if col.dtype != torch.float64:
+            raise RfxError(f"{what}: an f64 column is expected")
+        out = torch.empty_like(col)
+        self._operands_written()
+        self._xcheck(self.lib.rfx_exec_round(self._x, op, self._pieces(col), col.numel(), self._pieces(out), -1), what)
+        return out
+
+    def floor(self, col: torch.Tensor) -> torch.Tensor: return self._round(L.RFX_ROUND_FLOOR, col, "floor")
+    def ceil(self, col: torch.Tensor) -> torch.Tensor: return self._round(L.RFX_ROUND_CEIL, col, "ceil")
+    def round(self, col: torch.Tensor) -> torch.Tensor: return self._round(L.RFX_ROUND_ROUND, col, "round")
+
+    def neg(self, col: torch.Tensor) -> torch.Tensor:
+        """(neg col): int32 / int64 columns answer i64, float64 answers f64 (ray_neg's vector arms)."""
+        self._check_col(col)
+        t = {torch.int32: L.RFX_I32, torch.int64: L.RFX_I64, torch.float64: L.RFX_F64}.get(col.dtype)
+        if t is None:
+            raise RfxError(f"neg: unsupported dtype {col.dtype}")
+        out = torch.empty(col.numel(), dtype=torch.float64 if t == L.RFX_F64 else torch.int64, device=self.device)
+        self._operands_written()
+        self._xcheck(self.lib.rfx_exec_neg(self._x, t, self._pieces(col), col.numel(), self._pieces(out), -1), "neg")
+        return out
+
     def eval_expr(self, expr, table=None) -> torch.Tensor:
         """``(op x y)`` / an expression tree over columns and atoms as a device column: ray_add .. ray_mod (binop_map,
         core/math.c:2280-2345) in ONE pass whatever the depth."""
