@@ -87,11 +87,13 @@ enum {
     RFX_Q_WANT_FIRST = 4,       /* rfx_groups_t.d_first is wanted (the groups' first rows: costs one more result column) */
     RFX_Q_NO_SMALL = 8,         /* never the one-launch rank + emit of small dense tables (tests) */
     RFX_Q_PROBE_FIRST = 16,     /* hashed path, one shard: also leave, per row, the first row of its group (rfx_groups_t.d_probe) */
-    RFX_Q_SLICED = 32           /* the caller reads the result through rfx_exec_groups_fetch_all only: the planner may leave it as SLICES -- after the
+    RFX_Q_SLICED = 32,          /* the caller reads the result through rfx_exec_groups_fetch_all only: the planner may leave it as SLICES -- after the
                                  * merge every device holds the whole tables, ranks them (the same order everywhere) and emits only ITS range of the
                                  * groups; fetch_all copies every slice into the host columns from the owning shard's own thread, over its own PCIe
                                  * link (rfx_groups_t.nslices / slice[]).  Without the flag -- or with one device, or with FIRST aggregates -- the
                                  * whole result is on shard 0 as before (nslices == 1) */
+    RFX_Q_ROWS_DIRECT = 64,     /* rfx_exec_filter only: the compaction's masked-store write-out, whatever ships (measurements, tests) */
+    RFX_Q_ROWS_RING = 128       /* ... its LDS-ring write-out */
 };
 #define RFX_EXEC_NULL_KEY 1 /* positive: not an error, see RFX_Q_REFUSE_NULL_KEY */
 
@@ -302,6 +304,34 @@ int rfx_exec_round(rfx_exec_t *x, int op, const void *const *d_ins, int64_t n, v
 int rfx_exec_neg(rfx_exec_t *x, int32_t type, const void *const *d_ins, int64_t n, void *const *d_outs, int shard);
 int rfx_exec_within(rfx_exec_t *x, const void *const *d_cols, int64_t lo, int64_t hi, int64_t n, void *const *d_masks, int shard);
 
+/* ---- row verbs (rfx_rows.hip): filter, take, reverse ----
+ * Columns are given with their cell kind (RFX_ROWS_8 / RFX_ROWS_4W / RFX_ROWS_1, include/rfx_hip.h): 8-byte cells; an I32-family column's widened 8-byte
+ * copy, answered in 4-byte cells; B8 bytes.
+ * rfx_exec_filter (ray_filter, core/items.c:338-396): the rows of `ncols` columns that q selects -- q is what rfx_exec_where takes: a byte mask (d_mask)
+ *   or a predicate tree, so a fused where: feeds the compaction with no mask and no ids in between -- in row order.  pieces[k].d[s] is column k's address
+ *   on shard s (its rows rfx_exec_split(q->nrows, S, s)); every shard selects and compacts its own rows (one bitmap and one scan per shard, however many
+ *   columns: more than RFX_MAX_KEYS take several launches over them), and the result is the shards' pieces in shard order: count[s] cells of column k at
+ *   rfx_exec_rows_piece(out, s, k) on shard s's device (NULL when count[s] == 0), exact-size, one block per shard, 256-byte aligned pieces.  Returns with
+ *   the shards' streams idle when there is more than one.  RFX_Q_ROWS_DIRECT / RFX_Q_ROWS_RING in q->flags pick the write-out form.
+ * rfx_exec_take (ray_take, core/items.c:398-734): d_outs[k][i] = cell (j0 + i) mod l of d_cols[k] for i < m -- the caller has turned the count (its
+ *   sign, the cyclic start (l - m % l) * (count < 0)) or the [start amount] range (clamped) into j0 and m: 0 <= j0 < l unless m == 0.  rfx_exec_take_atom:
+ *   m cells of an atom (`bits`: the cell in the low bytes).  rfx_exec_reverse (ray_reverse, core/compose.c:144-202): d_out[i] = cell l - 1 - i.
+ *   One shard only: RFX_ELIMIT "take over a sharded table" / "reverse over a sharded table", as the sort.  Results 16-byte aligned.
+ * RFX_XSTAT_ROWS_FILTERS / _TAKES / _REVERSES count the calls, RFX_XSTAT_ROWS_IN / _OUT the rows read and answered. */
+typedef struct rfx_rows {
+    int32_t nshards, ncols;
+    int64_t total;                   /* selected rows over all shards */
+    int64_t count[RFX_MAX_SHARDS];   /* ... per shard */
+    void *d_block[RFX_MAX_SHARDS];   /* the shard's block on its device; NULL when count == 0 */
+    size_t *col_off;                 /* [shard * ncols + col]: where the column's piece starts in the shard's block (bytes) */
+} rfx_rows_t;
+int rfx_exec_filter(rfx_exec_t *x, const rfx_query_t *q, const rfx_qcol_t *pieces, const int32_t *kinds, int ncols, rfx_rows_t *out);
+void *rfx_exec_rows_piece(const rfx_rows_t *r, int shard, int col);
+void rfx_exec_rows_free(rfx_exec_t *x, rfx_rows_t *r);
+int rfx_exec_take(rfx_exec_t *x, const void *const *d_cols, const int32_t *kinds, int ncols, int64_t l, int64_t j0, int64_t m, void *const *d_outs);
+int rfx_exec_take_atom(rfx_exec_t *x, int32_t kind, uint64_t bits, int64_t m, void *d_out);
+int rfx_exec_reverse(rfx_exec_t *x, const void *d_col, int32_t kind, int64_t l, void *d_out);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -341,7 +371,12 @@ enum {
     RFX_XSTAT_XRANKS = 28,        /* xrank calls answered by the device path */
     RFX_XSTAT_XRANK_SORTED = 29,  /* ... of which an ASC / DESC attribute answered without a sort */
     RFX_XSTAT_BUCKET_MAPS = 30,   /* element-wise bucket maps run: xbar, floor / ceil / round, neg, within (one per call or operator piece) */
-    RFX_XSTAT_N = 31
+    RFX_XSTAT_ROWS_FILTERS = 31,  /* filter calls answered by the device path */
+    RFX_XSTAT_ROWS_TAKES = 32,    /* take calls (a table counts once) */
+    RFX_XSTAT_ROWS_REVERSES = 33, /* reverse calls */
+    RFX_XSTAT_ROWS_IN = 34,       /* rows the row verbs read: the table's rows (filter), the column's length (take, reverse; an atom counts 1) */
+    RFX_XSTAT_ROWS_OUT = 35,      /* ... and rows they answered */
+    RFX_XSTAT_N = 36
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

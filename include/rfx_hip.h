@@ -794,6 +794,27 @@ int rfx_hip_round_f64(rfx_ctx_t *ctx, int op, const double *d_in, int64_t n, dou
 int rfx_hip_neg(rfx_ctx_t *ctx, int32_t type, const void *d_in, int64_t n, void *d_out);
 int rfx_hip_within_i64(rfx_ctx_t *ctx, const int64_t *d_col, int64_t lo, int64_t hi, int64_t n, int8_t *d_mask);
 
+/* ---- row verbs (rfx_rows.hip): filter, take, reverse -- rows out of columns, cell for cell ----
+ * A column is given with its CELL KIND = the bytes of one OUTPUT cell: RFX_ROWS_8 (8-byte cells in and out: I64 / SYMBOL / TIMESTAMP / F64),
+ * RFX_ROWS_4W (an I32-family column's widened 8-byte copy in, rfx_hip_widen_i32, 4-byte cells out: NULL_I64 -> INT32_MIN, else the low 32 bits),
+ * RFX_ROWS_1 (B8: 1-byte cells in and out).
+ * rfx_hip_rows_compact: after a successful rfx_hip_where_begin (mask or predicate form) over the columns' rows: d_outs[k][r] = the cell of
+ *   d_cols[k] at the r-th selected row, for 1 .. RFX_MAX_KEYS columns in ONE launch (the bitmap is read once per launch); every output holds
+ *   exactly the `count` cells where_begin reported.  Several launches may follow one where_begin: the bitmap and the scanned offsets stay.  A wave
+ *   owns a contiguous run of 512-row chunks and so a contiguous run of every output.  form: RFX_ROWS_DIRECT -- masked stores straight from the
+ *   lanes; RFX_ROWS_RING -- the selected cells go through a wave-private LDS ring per column and leave as whole aligned 64-cell lines;
+ *   RFX_ROWS_FORM_DEFAULT -- the one that ships.  8-byte and widened columns 16-byte aligned.
+ * rfx_hip_rows_take: d_out[i] = cell (j0 + i) mod l of d_col for i < m (0 <= j0 < l, or j0 == l == 0 with m == 0).  j0 + m <= l (head, tail,
+ *   range): a streaming copy; else every thread owns a contiguous run of output cells, takes ONE remainder at its first cell and wraps by
+ *   compare-and-subtract.  d_out 16-byte aligned and not overlapping d_col.
+ * rfx_hip_rows_reverse: d_out[i] = cell l - 1 - i of d_col.   rfx_hip_rows_fill: m cells of `bits` (the cell in the low bytes). */
+enum { RFX_ROWS_8 = 8, RFX_ROWS_4W = 4, RFX_ROWS_1 = 1 };
+enum { RFX_ROWS_FORM_DEFAULT = 0, RFX_ROWS_DIRECT = 1, RFX_ROWS_RING = 2 };
+int rfx_hip_rows_compact(rfx_ctx_t *ctx, const void *const *d_cols, const int32_t *kinds, int ncols, void *const *d_outs, int form);
+int rfx_hip_rows_take(rfx_ctx_t *ctx, const void *d_col, int32_t kind, int64_t l, int64_t j0, int64_t m, void *d_out);
+int rfx_hip_rows_reverse(rfx_ctx_t *ctx, const void *d_col, int32_t kind, int64_t l, void *d_out);
+int rfx_hip_rows_fill(rfx_ctx_t *ctx, int32_t kind, uint64_t bits, int64_t m, void *d_out);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

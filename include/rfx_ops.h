@@ -237,6 +237,26 @@ rfx_obj_p rfx_neg(rfx_obj_p x);
 /* 1: the last of those seven calls was answered by the device path (an empty vector included: no launch); 0: it went to the host or failed */
 int rfx_last_bucket_on_gpu(void);
 
+/* The row verbs as built-ins of their own (rfx_rows.hip): rows out of vectors and tables, every result fresh host vectors (a table: a fresh table of them)
+ * with the reference's cells, type codes and attributes.  "A row type" below: I64 / SYMBOL / TIMESTAMP / F64 / I32 / DATE / TIME / B8.
+ *   binary_f (filter x mask)  ray_filter   core/items.c:338-396    x a vector of a row type or a TABLE whose every column is one (host vectors or device-column
+ *       handles); mask a B8 vector of the same length, a host vector or a device-column handle; any non-zero mask byte selects its row.  Runs over every
+ *       shard's rows: the mask goes to a 1-bit selection and straight into the ordered compaction of all columns.
+ *   binary_f (take from count) ray_take    core/items.c:398-734    from a vector or an atom of a row type, or a TABLE of such columns; count an -I64 / -I32 /
+ *       -I16 atom (negative: from the end; cyclic beyond the length: j0 = (l - m % l) * (count < 0)) or an I64 vector [start amount] (a negative start
+ *       counts from the end; clamped to the rows there are).
+ *   unary_f  (reverse x)       ray_reverse core/compose.c:144-202  a vector of a row type; ATTR_ASC and ATTR_DESC change places, the other attributes stay.
+ * The host's own verb answers everything else -- I16 / U8 / C8 / GUID / LIST / ENUM / MAPLIST / DICT, parted tables, a table without columns or with
+ * columns of unequal length, 4-byte device-column handles; whatever the reference answers with an error of its own wording (a mask that is not B8,
+ * lengths that differ, a negative range amount, a count of another type, reverse of a table); a count take from an empty vector or table (the reference
+ * divides by its length), a count of INT64_MIN, a range whose start + amount leaves 63 bits; take and reverse over more than one shard; a filter naming
+ * more than 63 columns when there is more than one shard; a result the device has no room for.  Without a host those are refused with the reason, which is also in rfx_ops_last_error(). */
+rfx_obj_p rfx_filter(rfx_obj_p x, rfx_obj_p mask);
+rfx_obj_p rfx_take(rfx_obj_p from, rfx_obj_p count);
+rfx_obj_p rfx_reverse(rfx_obj_p x);
+/* 1: the last of those three calls was answered by the device path (an empty result included: no launch); 0: it went to the host or failed */
+int rfx_last_rows_on_gpu(void);
+
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns
  * carry the mapping's values at the selected rows (value i at row ids[i]; under by: every group's aggregate at all of its selected

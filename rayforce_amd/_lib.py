@@ -134,6 +134,10 @@ RFX_XSTAT_SORTS, RFX_XSTAT_SORT_PASSES = 16, 17
 RFX_XSTAT_ASOF_JOINS, RFX_XSTAT_BINS, RFX_XSTAT_SEARCHES, RFX_XSTAT_NS_ASOF_BUILD, RFX_XSTAT_NS_ASOF_PROBE = 18, 19, 20, 21, 22
 RFX_XSTAT_SET_DISTINCTS, RFX_XSTAT_SET_MEMBERS, RFX_XSTAT_SET_FILTERS, RFX_XSTAT_NS_SET_BUILD, RFX_XSTAT_NS_SET_PROBE = 23, 24, 25, 26, 27
 RFX_XSTAT_XRANKS, RFX_XSTAT_XRANK_SORTED, RFX_XSTAT_BUCKET_MAPS = 28, 29, 30
+RFX_XSTAT_ROWS_FILTERS, RFX_XSTAT_ROWS_TAKES, RFX_XSTAT_ROWS_REVERSES, RFX_XSTAT_ROWS_IN, RFX_XSTAT_ROWS_OUT = 31, 32, 33, 34, 35
+RFX_Q_ROWS_DIRECT, RFX_Q_ROWS_RING = 64, 128
+RFX_ROWS_8, RFX_ROWS_4W, RFX_ROWS_1 = 8, 4, 1  # include/rfx_hip.h: a column's cell kind = the bytes of one result cell
+RFX_ROWS_FORM_DEFAULT, RFX_ROWS_DIRECT, RFX_ROWS_RING = 0, 1, 2
 RFX_XRANK_ASC, RFX_XRANK_DESC = 2, 4
 RFX_SET_ROUTE_UNDEFINED, RFX_SET_ROUTE_NONE, RFX_SET_ROUTE_DENSE, RFX_SET_ROUTE_HASH, RFX_SET_ROUTE_DISJOINT, RFX_SET_ROUTE_ATOM = -1, 0, 1, 2, 3, 4
 RFX_WAGG = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "first": 5, "last": 6}  # include/rfx_hip.h RFX_WAGG_*
@@ -153,6 +157,11 @@ class Query(C.Structure):
 
 class Ids(C.Structure):
     _fields_ = [("nshards", C.c_int32), ("total", C.c_int64), ("count", C.c_int64 * RFX_MAX_SHARDS), ("d_ids", C.c_void_p * RFX_MAX_SHARDS)]
+
+
+class Rows(C.Structure):  # rfx_rows_t
+    _fields_ = [("nshards", C.c_int32), ("ncols", C.c_int32), ("total", C.c_int64), ("count", C.c_int64 * RFX_MAX_SHARDS),
+                ("d_block", C.c_void_p * RFX_MAX_SHARDS), ("col_off", C.POINTER(C.c_size_t))]
 
 
 class GSlice(C.Structure):
@@ -304,6 +313,10 @@ PROTOTYPES = {
     "rfx_hip_round_f64": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_neg": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_within_i64": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_rows_compact": (C.c_int, [_ctx, _P(C.c_void_p), _P(C.c_int32), C.c_int, _P(C.c_void_p), C.c_int]),
+    "rfx_hip_rows_take": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_rows_reverse": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "rfx_hip_rows_fill": (C.c_int, [_ctx, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_set_scope": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_int64)]),
@@ -385,6 +398,12 @@ EXEC_PROTOTYPES = {
     "rfx_exec_round": (C.c_int, [_exec, C.c_int, _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
     "rfx_exec_neg": (C.c_int, [_exec, C.c_int32, _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
     "rfx_exec_within": (C.c_int, [_exec, _P(C.c_void_p), C.c_int64, C.c_int64, C.c_int64, _P(C.c_void_p), C.c_int]),
+    "rfx_exec_filter": (C.c_int, [_exec, _P(Query), _P(QCol), _P(C.c_int32), C.c_int, _P(Rows)]),
+    "rfx_exec_rows_piece": (C.c_void_p, [_P(Rows), C.c_int, C.c_int]),
+    "rfx_exec_rows_free": (None, [_exec, _P(Rows)]),
+    "rfx_exec_take": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_int32), C.c_int, C.c_int64, C.c_int64, C.c_int64, _P(C.c_void_p)]),
+    "rfx_exec_take_atom": (C.c_int, [_exec, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
+    "rfx_exec_reverse": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_bin": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,

@@ -91,3 +91,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_window.c"
 #include "rfx_exec_set.c"
 #include "rfx_exec_bucket.c"
+#include "rfx_exec_rows.c"

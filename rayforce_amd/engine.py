@@ -477,6 +477,129 @@ class Engine:
         self._xcheck(self.lib.rfx_exec_neg(self._x, t, self._pieces(col), col.numel(), self._pieces(out), -1), "neg")
         return out
 
+    # ------------------------------------------------------------------ row verbs (rfx_rows.hip through rfx_exec_rows.c)
+    _ROW_TYPESTR = {torch.int64: "<i8", torch.float64: "<f8", torch.int32: "<i4", torch.int8: "|i1"}
+
+    def _row_source(self, t: torch.Tensor, n: Optional[int] = None):
+        """A column of a row verb -> (the tensor the kernels read, its cell kind, the result's dtype): i64 / f64 cells as they are, int8 (bool) bytes,
+        an int32 column through its widened 8-byte copy (rfx_hip_widen_i32), answered in 4-byte cells again."""
+        if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+            t = t.view(torch.int8)
+        self._check_col(t, n)
+        if t.dtype in (torch.int64, torch.float64):
+            return t, L.RFX_ROWS_8, t.dtype
+        if t.dtype == torch.int8:
+            return t, L.RFX_ROWS_1, t.dtype
+        if t.dtype == torch.int32:
+            wide = torch.empty(t.numel(), dtype=torch.int64, device=self.device)
+            L.check(self.lib.rfx_hip_widen_i32(self._ctx, t.data_ptr(), t.numel(), wide.data_ptr()), "widen_i32")
+            return wide, L.RFX_ROWS_4W, t.dtype
+        raise RfxError(f"unsupported column dtype {t.dtype} (the row verbs take int64, float64, int32 and int8 / bool columns)")
+
+    def _row_view(self, owner, ptr, n: int, dtype) -> torch.Tensor:
+        if not n or not ptr:
+            return self.empty(0, dtype)
+        return torch.as_tensor(_View(owner, ptr, n, self._ROW_TYPESTR[dtype]), device=self.device)
+
+    def filter(self, columns, where, table=None, form: Optional[str] = None):
+        """(filter x mask) / the rows a where: selects: ``columns`` is one device column or a dict of them, ``where`` a B8 mask tensor or a predicate
+        tree exactly as Engine.where takes it -- the fused pass feeds the ordered compaction with no mask and no ids in between (rfx_exec_filter).
+        Runs over every shard's rows.  ``form``: None (what ships), "direct" or "ring" -- the compaction's write-out (measurements).  (syncs)"""
+        single = isinstance(columns, torch.Tensor)
+        cols = {"": columns} if single else dict(columns)
+        if not cols:
+            raise RfxError("filter: no columns")
+        n = next(iter(cols.values())).numel()
+        if form not in (None, "direct", "ring"):
+            raise RfxError(f"filter: unknown write-out form {form!r}")
+        flags = {None: 0, "direct": L.RFX_Q_ROWS_DIRECT, "ring": L.RFX_Q_ROWS_RING}[form]
+        q, _ = self._query(where, [], table, n, flags=flags)
+        srcs = [self._row_source(t, n) for t in cols.values()]
+        self._operands_written()
+        pieces = (L.QCol * len(srcs))()
+        kinds = (C.c_int32 * len(srcs))()
+        for k, (t, kind, _dt) in enumerate(srcs):
+            addr = self._pieces(t)
+            for s in range(self.shards):
+                pieces[k].d[s] = addr[s]
+            kinds[k] = kind
+        rows = L.Rows()
+        self._xcheck(self.lib.rfx_exec_filter(self._x, C.byref(q), pieces, kinds, len(srcs), C.byref(rows)), "filter")
+        owner = _Owner(self, rows, self.lib.rfx_exec_rows_free)
+        total, out = int(rows.total), []
+        for k, (_t, kind, dt) in enumerate(srcs):
+            if rows.nshards == 1:
+                out.append(self._row_view(owner, self.lib.rfx_exec_rows_piece(C.byref(rows), 0, k), total, dt))
+                continue
+            o, at = self.empty(total, dt), 0
+            for s in range(rows.nshards):  # shard order = row order
+                if rows.count[s]:
+                    L.check(self.lib.rfx_hip_d2d(self._ctx, o.data_ptr() + at, C.c_void_p(self.lib.rfx_exec_rows_piece(C.byref(rows), s, k)), rows.count[s] * kind), "d2d")
+                    at += rows.count[s] * kind
+            out.append(o)
+        if rows.nshards > 1:
+            self.sync()
+        return out[0] if single else dict(zip(cols.keys(), out))
+
+    @staticmethod
+    def _take_window(l: int, count):
+        """ray_take's count (core/items.c:405-445) -> (first cell, cells): an int takes |count| cells cyclically, from the end when negative; a
+        (start, amount) pair takes a range clamped to the cells there are, a negative start counting from the end."""
+        if isinstance(count, (tuple, list)):
+            if len(count) != 2 or int(count[1]) < 0:
+                raise RfxError("take: a range is (start, amount) with amount >= 0")  # reference: err_length
+            start, m = int(count[0]), int(count[1])
+            if start < 0:
+                start += l
+            start = min(max(start, 0), l)
+            m = min(m, l - start)
+            return (start if m else 0), m
+        c = int(count)
+        if l == 0:
+            raise RfxError("take from an empty column")  # (the reference divides by the length)
+        m = abs(c)
+        return ((l - m % l) % l if c < 0 else 0), m
+
+    def take(self, columns, count, dtype=None):
+        """(take from count): ``columns`` is one device column, a dict of them, or a Python number (an atom, broadcast as ``dtype``: int64 / float64 /
+        int32 / int8); ``count`` an int or a (start, amount) pair.  One shard (rfx_exec_take)."""
+        if isinstance(columns, (int, float, bool)):
+            import struct
+            dt = dtype or (torch.float64 if isinstance(columns, float) else torch.int64)
+            if isinstance(count, (tuple, list)) and len(count) != 2:
+                raise RfxError("take: a range is (start, amount) with amount >= 0")
+            m = abs(int(count)) if not isinstance(count, (tuple, list)) else int(count[1])
+            if dt not in self._ROW_TYPESTR or m < 0:
+                raise RfxError("take: an atom is broadcast as int64, float64, int32 or int8, a non-negative number of times")
+            out = self.empty(m, dt)
+            fmt = {torch.int64: "<q", torch.float64: "<d", torch.int32: "<i", torch.int8: "<b"}[dt]
+            bits = int.from_bytes(struct.pack(fmt, float(columns) if dt == torch.float64 else int(columns)), "little")
+            if m:
+                self._xcheck(self.lib.rfx_exec_take_atom(self._x, out.element_size(), bits, m, out.data_ptr()), "take")
+            return out
+        single = isinstance(columns, torch.Tensor)
+        cols = {"": columns} if single else dict(columns)
+        if not cols:
+            raise RfxError("take: no columns")
+        l = next(iter(cols.values())).numel()
+        j0, m = self._take_window(l, count)
+        srcs = [self._row_source(t, l) for t in cols.values()]
+        outs = [self.empty(m, dt) for _t, _k, dt in srcs]
+        if m:
+            ptrs = (C.c_void_p * len(srcs))(*[t.data_ptr() for t, _k, _d in srcs])
+            kinds = (C.c_int32 * len(srcs))(*[k for _t, k, _d in srcs])
+            optrs = (C.c_void_p * len(srcs))(*[o.data_ptr() for o in outs])
+            self._xcheck(self.lib.rfx_exec_take(self._x, ptrs, kinds, len(srcs), l, j0, m, optrs), "take")
+        return outs[0] if single else dict(zip(cols.keys(), outs))
+
+    def reverse(self, col: torch.Tensor) -> torch.Tensor:
+        """(reverse col): the column's cells last to first (rfx_exec_reverse).  One shard."""
+        t, kind, dt = self._row_source(col)
+        out = self.empty(t.numel(), dt)
+        if t.numel():
+            self._xcheck(self.lib.rfx_exec_reverse(self._x, t.data_ptr(), kind, t.numel(), out.data_ptr()), "reverse")
+        return out
+
     def eval_expr(self, expr, table=None) -> torch.Tensor:
         """``(op x y)`` / an expression tree over columns and atoms as a device column: ray_add .. ray_mod (binop_map,
         core/math.c:2280-2345) in ONE pass whatever the depth."""

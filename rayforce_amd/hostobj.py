@@ -57,6 +57,10 @@ OPS_PROTOTYPES = {
     **{f"rfx_{n}": (C.c_void_p, [C.c_void_p, C.c_void_p]) for n in ("xrank", "xbar", "within")},
     **{f"rfx_{n}": (C.c_void_p, [C.c_void_p]) for n in ("floor", "ceil", "round", "neg")},
     "rfx_last_bucket_on_gpu": (C.c_int, []),
+    "rfx_filter": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "rfx_take": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "rfx_reverse": (C.c_void_p, [C.c_void_p]),
+    "rfx_last_rows_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),
