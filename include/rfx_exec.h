@@ -332,6 +332,13 @@ int rfx_exec_take(rfx_exec_t *x, const void *const *d_cols, const int32_t *kinds
 int rfx_exec_take_atom(rfx_exec_t *x, int32_t kind, uint64_t bits, int64_t m, void *d_out);
 int rfx_exec_reverse(rfx_exec_t *x, const void *d_col, int32_t kind, int64_t l, void *d_out);
 
+/* ---- cast (rfx_cast.hip) ----
+ * rfx_exec_cast: rfx_hip_cast over every shard's rows, like the element-wise bucket verbs: d_ins[s] / d_outs[s] are shard s's pieces (rows
+ *   rfx_exec_split(n, S, s)) of the source and of the result; src_type / dst_type as rfx_hip_cast takes them (RFX_CAST_*, | RFX_CAST_WIDENED).  shard < 0:
+ *   all shards, n the whole length, returns with the shards' streams idle when there is more than one; shard >= 0: that shard's piece alone, n ITS rows,
+ *   enqueued on its context.  RFX_EINVAL: the reference has no such arm (rfx_hip_cast_arm); RFX_ELIMIT: several ranks.  RFX_XSTAT_CASTS counts. */
+int rfx_exec_cast(rfx_exec_t *x, int32_t src_type, int32_t dst_type, const void *const *d_ins, int64_t n, void *const *d_outs, int shard);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -376,7 +383,8 @@ enum {
     RFX_XSTAT_ROWS_REVERSES = 33, /* reverse calls */
     RFX_XSTAT_ROWS_IN = 34,       /* rows the row verbs read: the table's rows (filter), the column's length (take, reverse; an atom counts 1) */
     RFX_XSTAT_ROWS_OUT = 35,      /* ... and rows they answered */
-    RFX_XSTAT_N = 36
+    RFX_XSTAT_CASTS = 36,         /* casts run (one per call or operator piece) */
+    RFX_XSTAT_N = 37
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

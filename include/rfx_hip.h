@@ -815,6 +815,22 @@ int rfx_hip_rows_take(rfx_ctx_t *ctx, const void *d_col, int32_t kind, int64_t l
 int rfx_hip_rows_reverse(rfx_ctx_t *ctx, const void *d_col, int32_t kind, int64_t l, void *d_out);
 int rfx_hip_rows_fill(rfx_ctx_t *ctx, int32_t kind, uint64_t bits, int64_t m, void *d_out);
 
+/* ---- cast (rfx_cast.hip): `as` over vectors of the nine numeric and temporal types ----
+ * rfx_hip_cast: d_dst[i] = (dst cell type) d_src[i] for i < n, cast_obj's vector arms (core/rayforce.c:2558-2752): one plain C cast per cell as the
+ *   reference's x86 build computes it, nulls NOT carried.  src_type / dst_type are the reference's vector type codes (RFX_CAST_*); a 4-byte source
+ *   held as its widened 8-byte image (rfx_hip_widen_i32: what the operator layer's resident copies are) is its code | RFX_CAST_WIDENED, the null's
+ *   promotion undone.  Integer -> narrower integer keeps the low bytes (a B8 result is the low byte, not != 0); a narrower integer is sign-extended, a
+ *   B8 / U8 cell zero-extended; integer -> F64 is (double)x (NULL_I64 -> -2^63, not NaN); F64 -> I64 / TIMESTAMP truncates, a NaN, an infinity and
+ *   anything outside [-2^63, 2^63) -> INT64_MIN; F64 -> I32 / DATE / TIME truncates, whatever does not land in the i32 range -> INT32_MIN; F64 -> I16 /
+ *   U8 / B8 is that 32-bit conversion's low 16 / 8 bits.  Types of one cell class (I32 / DATE / TIME, I64 / TIMESTAMP) copy.
+ *   d_src and d_dst 16-byte aligned, d_dst a buffer of its own.
+ * rfx_hip_cast_arm: 1 when the reference has a vector arm from src_type to dst_type that runs a loop: both among the nine, not the same type (clone_obj),
+ *   not B8 <-> U8 (its type error).  Host only. */
+enum { RFX_CAST_B8 = 1, RFX_CAST_U8 = 2, RFX_CAST_I16 = 3, RFX_CAST_I32 = 4, RFX_CAST_I64 = 5, RFX_CAST_DATE = 7, RFX_CAST_TIME = 8, RFX_CAST_TIMESTAMP = 9,
+       RFX_CAST_F64 = 10, RFX_CAST_WIDENED = 0x100 };
+int rfx_hip_cast(rfx_ctx_t *ctx, int32_t src_type, int32_t dst_type, const void *d_src, int64_t n, void *d_dst);
+int rfx_hip_cast_arm(int32_t src_type, int32_t dst_type);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -257,6 +257,19 @@ rfx_obj_p rfx_reverse(rfx_obj_p x);
 /* 1: the last of those three calls was answered by the device path (an empty result included: no launch); 0: it went to the host or failed */
 int rfx_last_rows_on_gpu(void);
 
+/* `as` as a built-in of its own (rfx_cast.hip):
+ *   binary_f (as 'T x)  ray_cast_obj  core/compose.c:42-68, cast_obj core/rayforce.c:2312-2831   'T a symbol atom naming one of B8 U8 I16 I32 I64 F64 DATE
+ *       TIME TIMESTAMP by its vector name or its atom name ('i32 answers as 'I32 over a vector); x a plain vector of one of those nine types, a host vector
+ *       or an I64 / F64 / TIMESTAMP / B8 device-column handle.  One C cast per cell, nulls not carried (rfx_hip.h, rfx_hip_cast).  The same type answers a
+ *       clone of x (its attributes with it), an empty x an empty vector of the target type, every other pair a fresh host vector of the target type,
+ *       attribute byte 0.  Runs over every shard's rows.
+ * The host's own verb answers everything else -- atoms, LIST / C8 / SYMBOL / GUID / ENUM vectors, tables and dicts, a type name that is no symbol atom or
+ * names another type, B8 <-> U8 (the reference has no such arm: its type error), 4-byte / 2-byte / U8 device-column handles, a result the device has no
+ * room for.  Without a host those are refused with the reason, which is also in rfx_ops_last_error(). */
+rfx_obj_p rfx_as(rfx_obj_p type_name, rfx_obj_p x);
+/* 1: the last rfx_as was answered by the device path (a clone and an empty vector included: no launch); 0: it went to the host or failed */
+int rfx_last_cast_on_gpu(void);
+
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns
  * carry the mapping's values at the selected rows (value i at row ids[i]; under by: every group's aggregate at all of its selected

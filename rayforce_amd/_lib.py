@@ -136,6 +136,10 @@ RFX_XSTAT_SET_DISTINCTS, RFX_XSTAT_SET_MEMBERS, RFX_XSTAT_SET_FILTERS, RFX_XSTAT
 RFX_XSTAT_XRANKS, RFX_XSTAT_XRANK_SORTED, RFX_XSTAT_BUCKET_MAPS = 28, 29, 30
 RFX_XSTAT_ROWS_FILTERS, RFX_XSTAT_ROWS_TAKES, RFX_XSTAT_ROWS_REVERSES, RFX_XSTAT_ROWS_IN, RFX_XSTAT_ROWS_OUT = 31, 32, 33, 34, 35
 RFX_Q_ROWS_DIRECT, RFX_Q_ROWS_RING = 64, 128
+RFX_XSTAT_CASTS = 36
+# include/rfx_hip.h RFX_CAST_*: the reference's vector type codes rfx_hip_cast / rfx_exec_cast take
+RFX_CAST = {"b8": 1, "u8": 2, "i16": 3, "i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}
+RFX_CAST_WIDENED = 0x100
 RFX_ROWS_8, RFX_ROWS_4W, RFX_ROWS_1 = 8, 4, 1  # include/rfx_hip.h: a column's cell kind = the bytes of one result cell
 RFX_ROWS_FORM_DEFAULT, RFX_ROWS_DIRECT, RFX_ROWS_RING = 0, 1, 2
 RFX_XRANK_ASC, RFX_XRANK_DESC = 2, 4
@@ -317,6 +321,8 @@ PROTOTYPES = {
     "rfx_hip_rows_take": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "rfx_hip_rows_reverse": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "rfx_hip_rows_fill": (C.c_int, [_ctx, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
+    "rfx_hip_cast": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rfx_hip_cast_arm": (C.c_int, [C.c_int32, C.c_int32]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_set_scope": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_int64)]),
@@ -404,6 +410,7 @@ EXEC_PROTOTYPES = {
     "rfx_exec_take": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_int32), C.c_int, C.c_int64, C.c_int64, C.c_int64, _P(C.c_void_p)]),
     "rfx_exec_take_atom": (C.c_int, [_exec, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
     "rfx_exec_reverse": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "rfx_exec_cast": (C.c_int, [_exec, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_bin": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,

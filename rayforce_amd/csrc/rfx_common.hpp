@@ -277,6 +277,10 @@ __device__ __forceinline__ int rfx_xbar_i32(int x, int y) {
 __device__ __forceinline__ i64 rfx_f64_to_i64_x86(double x) {
     return (x >= -9223372036854775808.0 && x < 9223372036854775808.0) ? (i64)x : RFX_NULL_I64_D;
 }
+// ... and its 32-bit form (cvttsd2si r32): whatever does not truncate into the i32 range, a NaN included, converts to INT32_MIN
+__device__ __forceinline__ int rfx_f64_to_i32_x86(double x) {
+    return (x > -2147483649.0 && x < 2147483648.0) ? (int)x : RFX_NULL_I32_D;
+}
 // The reference's build computes f64 with denormals-are-zero and flush-to-zero set (its unsafe-math link sets MXCSR so): a subnormal operand or result
 // is a signed zero there.  The device keeps subnormals, so the cells that meet one are flushed by hand.
 __device__ __host__ __forceinline__ u64 rfx_ftz_bits(u64 b) { return (b & 0x7FF0000000000000ULL) == 0 ? (b & 0x8000000000000000ULL) : b; }

@@ -92,3 +92,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_set.c"
 #include "rfx_exec_bucket.c"
 #include "rfx_exec_rows.c"
+#include "rfx_exec_cast.c"

@@ -55,14 +55,14 @@ static struct {
  * The ids after F_BINR lie outside the range: window_agg (rfx_ops_window.c) recognises F_LAST and refuses F_DEV; F_DISTINCT .. F_UNION (and F_IN as a
  * verb of its own) are the set verbs of rfx_ops_set.c, which no reader of fn_id maps -- inside where: F_IN stays the comparison list of
  * rfx_ops_plan.c and nothing else. */
-enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_DEV, F_XRANK, F_FLOOR, F_CEIL, F_ROUND, F_NEG, F_FILTER, F_REVERSE, F_N };
+enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_DEV, F_XRANK, F_FLOOR, F_CEIL, F_ROUND, F_NEG, F_FILTER, F_REVERSE, F_AS, F_N };
 static const char *HOST_FN[F_N] = {"ray_sum", "ray_avg", "ray_min", "ray_max", "ray_count", "ray_first", "ray_eq",  "ray_ne",  "ray_lt",  "ray_gt",
                                    "ray_le",  "ray_ge",  "ray_and", "ray_or",  "ray_select", "ray_add",  "ray_sub", "ray_mul", "ray_fdiv", "ray_div", "ray_mod", "ray_xbar",
                                    "ray_left_join", "ray_inner_join", "ray_update", "ray_take", "ray_in", "ray_within", "ray_not", "ray_med",
                                    "ray_iasc", "ray_idesc", "ray_asc", "ray_desc", "ray_rank", "ray_xasc", "ray_xdesc",
                                    "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last",
                                    "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union", "ray_dev",
-                                   "ray_xrank", "ray_floor", "ray_ceil", "ray_round", "ray_neg", "ray_filter", "ray_reverse"}; /* (not: recognised inside where: only; in / within also verbs of their own) */
+                                   "ray_xrank", "ray_floor", "ray_ceil", "ray_round", "ray_neg", "ray_filter", "ray_reverse", "ray_cast_obj"}; /* (not: recognised inside where: only; in / within also verbs of their own) */
 /* xbar inside `by:` is recognised by its function object (fn_id -> F_XBAR) and bucketed by the planner; called as a verb it is rfx_xbar
  * (rfx_ops_bucket.c), which the standalone object model binds to "xbar". */
 static void *OUR_FN[F_N];
@@ -90,7 +90,7 @@ int rfx_host_bind(void) {
     OUR_FN[F_WJ] = (void *)rfx_window_join; OUR_FN[F_WJ1] = (void *)rfx_window_join1; OUR_FN[F_LAST] = (void *)rfx_last; OUR_FN[F_DEV] = (void *)rfx_dev;
     OUR_FN[F_IN] = (void *)rfx_in; OUR_FN[F_DISTINCT] = (void *)rfx_distinct; OUR_FN[F_FIND] = (void *)rfx_find; OUR_FN[F_SECT] = (void *)rfx_sect;
     OUR_FN[F_EXCEPT] = (void *)rfx_except; OUR_FN[F_UNION] = (void *)rfx_union;
-    OUR_FN[F_TAKE] = (void *)rfx_take; OUR_FN[F_FILTER] = (void *)rfx_filter; OUR_FN[F_REVERSE] = (void *)rfx_reverse; /* (rfx_select's take: stays the host's: H.f[F_TAKE]) */
+    OUR_FN[F_TAKE] = (void *)rfx_take; OUR_FN[F_FILTER] = (void *)rfx_filter; OUR_FN[F_REVERSE] = (void *)rfx_reverse; OUR_FN[F_AS] = (void *)rfx_as; /* (rfx_select's take: stays the host's: H.f[F_TAKE]) */
     void *v = dlsym(RTLD_DEFAULT, "vector"), *t = dlsym(RTLD_DEFAULT, "table"), *e = dlsym(RTLD_DEFAULT, "eval");
     void *rs = dlsym(RTLD_DEFAULT, "ray_select"), *nu = dlsym(RTLD_DEFAULT, "__NULL_OBJ");
     if (v && t && e && rs && nu && !getenv("RFX_FORCE_STANDALONE")) {
@@ -149,7 +149,8 @@ obj_p rfx_host_fn(const char *name) {
         {"sect", F_SECT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"except", F_EXCEPT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"union", F_UNION, RFX_TYPE_BINARY, RFX_FN_NONE},
         {"xrank", F_XRANK, RFX_TYPE_BINARY, RFX_FN_NONE}, {"floor", F_FLOOR, RFX_TYPE_UNARY, RFX_FN_ATOMIC}, {"ceil", F_CEIL, RFX_TYPE_UNARY, RFX_FN_ATOMIC},
         {"round", F_ROUND, RFX_TYPE_UNARY, RFX_FN_ATOMIC}, {"neg", F_NEG, RFX_TYPE_UNARY, RFX_FN_ATOMIC},
-        {"filter", F_FILTER, RFX_TYPE_BINARY, RFX_FN_NONE}, {"take", F_TAKE, RFX_TYPE_BINARY, RFX_FN_NONE}, {"reverse", F_REVERSE, RFX_TYPE_UNARY, RFX_FN_NONE}};
+        {"filter", F_FILTER, RFX_TYPE_BINARY, RFX_FN_NONE}, {"take", F_TAKE, RFX_TYPE_BINARY, RFX_FN_NONE}, {"reverse", F_REVERSE, RFX_TYPE_UNARY, RFX_FN_NONE},
+        {"as", F_AS, RFX_TYPE_BINARY, RFX_FN_NONE}};
     rfx_host_bind();
     for (size_t i = 0; i < sizeof(T) / sizeof(T[0]); i++)
         if (strcmp(T[i].n, name) == 0) {
@@ -208,3 +209,4 @@ static int fn_id(obj_p o) {
 #include "rfx_ops_set.c"
 #include "rfx_ops_bucket.c"
 #include "rfx_ops_rows.c"
+#include "rfx_ops_cast.c"

@@ -477,6 +477,37 @@ class Engine:
         self._xcheck(self.lib.rfx_exec_neg(self._x, t, self._pieces(col), col.numel(), self._pieces(out), -1), "neg")
         return out
 
+    # ------------------------------------------------------------------ cast (rfx_cast.hip through rfx_exec_cast.c)
+    _CAST_DTYPE = {1: torch.int8, 2: torch.uint8, 3: torch.int16, 4: torch.int32, 5: torch.int64, 7: torch.int32, 8: torch.int32, 9: torch.int64, 10: torch.float64}
+    _CAST_OF_DTYPE = {torch.int8: 1, torch.bool: 1, torch.uint8: 2, torch.int16: 3, torch.int32: 4, torch.int64: 5, torch.float64: 10}
+
+    def cast(self, col: torch.Tensor, to: str, frm: Optional[str] = None) -> torch.Tensor:
+        """(as 'to col): a uint8 / int8 / int16 / int32 / int64 / float64 device column cast to the type ``to`` names ("b8" "u8" "i16" "i32" "i64" "f64"
+        "date" "time" "timestamp", either case), one C cast per cell as the reference does it, nulls not carried.  ``frm`` names the column's reference
+        type where the dtype does not (an int32 column is "i32" unless it is "date" / "time", an int64 one "i64" unless "timestamp", int8 "b8", uint8
+        "u8").  -> a tensor of the target's storage dtype (b8 int8, u8 uint8); the same type answers ``col`` itself."""
+        if isinstance(col, torch.Tensor) and col.dtype == torch.bool:
+            col = col.view(torch.int8)
+        self._check_col(col)
+        dst = L.RFX_CAST.get(str(to).lower())
+        if dst is None:
+            raise RfxError(f"cast: {to!r} names none of the nine numeric and temporal types")
+        src = L.RFX_CAST.get(str(frm).lower()) if frm is not None else self._CAST_OF_DTYPE.get(col.dtype)
+        if src is None or self._CAST_DTYPE[src] != col.dtype:
+            raise RfxError(f"cast: a {col.dtype} column cannot be {frm or 'cast'}")
+        if src == dst:
+            return col
+        out = torch.empty(col.numel(), dtype=self._CAST_DTYPE[dst], device=self.device)
+        if col.numel() == 0:
+            return out
+        if not self.lib.rfx_hip_cast_arm(src, dst):
+            raise RfxError(f"cast: the reference has no cast from type {src} to type {dst}")
+        if col.data_ptr() % 16:  # (a view into a larger tensor: the kernel moves 16-byte accesses)
+            col = col.clone()
+        self._operands_written()
+        self._xcheck(self.lib.rfx_exec_cast(self._x, src, dst, self._pieces(col), col.numel(), self._pieces(out), -1), "cast")
+        return out
+
     # ------------------------------------------------------------------ row verbs (rfx_rows.hip through rfx_exec_rows.c)
     _ROW_TYPESTR = {torch.int64: "<i8", torch.float64: "<f8", torch.int32: "<i4", torch.int8: "|i1"}
 

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib as L
 
 T_LIST, T_B8, T_I64, T_SYMBOL, T_F64, T_TABLE, T_DICT, T_ERR = 0, 1, 5, 6, 10, 98, 99, 127
-NP_OF = {T_B8: np.int8, T_I64: np.int64, T_SYMBOL: np.int64, T_F64: np.float64, 9: np.int64, 4: np.int32, 7: np.int32, 8: np.int32}
+NP_OF = {T_B8: np.int8, T_I64: np.int64, T_SYMBOL: np.int64, T_F64: np.float64, 9: np.int64, 4: np.int32, 7: np.int32, 8: np.int32, 2: np.uint8, 3: np.int16}
 TYPE_OF = {np.dtype(np.int8): T_B8, np.dtype(np.bool_): T_B8, np.dtype(np.int64): T_I64, np.dtype(np.float64): T_F64}
 
 OPS_PROTOTYPES = {
@@ -61,6 +61,8 @@ OPS_PROTOTYPES = {
     "rfx_take": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_reverse": (C.c_void_p, [C.c_void_p]),
     "rfx_last_rows_on_gpu": (C.c_int, []),
+    "rfx_as": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "rfx_last_cast_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),
