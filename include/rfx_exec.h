@@ -384,7 +384,8 @@ enum {
     RFX_XSTAT_ROWS_IN = 34,       /* rows the row verbs read: the table's rows (filter), the column's length (take, reverse; an atom counts 1) */
     RFX_XSTAT_ROWS_OUT = 35,      /* ... and rows they answered */
     RFX_XSTAT_CASTS = 36,         /* casts run (one per call or operator piece) */
-    RFX_XSTAT_N = 37
+    RFX_XSTAT_SCOPE_SPARSE_SAMPLED = 37, /* group-bys whose sampled key range alone sent them to the hashed tables (no exact scope pass) */
+    RFX_XSTAT_N = 38
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

@@ -137,6 +137,7 @@ RFX_XSTAT_XRANKS, RFX_XSTAT_XRANK_SORTED, RFX_XSTAT_BUCKET_MAPS = 28, 29, 30
 RFX_XSTAT_ROWS_FILTERS, RFX_XSTAT_ROWS_TAKES, RFX_XSTAT_ROWS_REVERSES, RFX_XSTAT_ROWS_IN, RFX_XSTAT_ROWS_OUT = 31, 32, 33, 34, 35
 RFX_Q_ROWS_DIRECT, RFX_Q_ROWS_RING = 64, 128
 RFX_XSTAT_CASTS = 36
+RFX_XSTAT_SCOPE_SPARSE_SAMPLED = 37
 # include/rfx_hip.h RFX_CAST_*: the reference's vector type codes rfx_hip_cast / rfx_exec_cast take
 RFX_CAST = {"b8": 1, "u8": 2, "i16": 3, "i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}
 RFX_CAST_WIDENED = 0x100

@@ -124,6 +124,7 @@ static int gb_scope(gq_t *G) {
                 if (!have && G->seen > 0 && G->kmin != NULL_I64 && G->kmax >= G->kmin && (uint64_t)G->kmax - (uint64_t)G->kmin + 1 > (uint64_t)q->nrows) {
                     G->seen = q->nrows;
                     G->sparse_sampled = 1;
+                    x->stat[RFX_XSTAT_SCOPE_SPARSE_SAMPLED]++;
                     have = 1;
                 }
                 if (!have && !any_xbar && G->kmin != NULL_I64) spec_remember_wide(x, G->spec_id, q->nrows); /* neither LDS-sized nor sparse: dense and wide */
@@ -286,6 +287,11 @@ static int gb_passes(gq_t *G) {
     }
 }
 
+/* the `first` cell of a hashed table's null entry, through the shard's layout: entry `cap` -- cell `cap` of the array-per-field form, cell cap * W
+ * of the PACKED form (entries of W = h->packed cells: hash_slot_ins_packed answers capacity * W for the null key).  Whoever addresses the null
+ * entry from the host asks here */
+static const int64_t *ht_null_first(const shard_t *h, int64_t cap) { return h->ht.d_first + cap * (h->packed ? h->packed : 1); }
+
 /* sparse keys routed by the sample alone: did a null key come by after all?  its slot is the tables' last */
 static int gb_null_slot(gq_t *G) {
     rfx_exec_t *x = G->x;
@@ -298,7 +304,7 @@ static int gb_null_slot(gq_t *G) {
         for (int s = 0; s < S && rc == RFX_OK; s++) {
             int64_t f = INF_I64;
             if (S > 1) rfx_hip_ctx_bind_thread(x->ctx[s]);
-            rc = rfx_hip_d2h(x->ctx[s], &f, sh[s].ht.d_first + G->cap, 8);
+            rc = rfx_hip_d2h(x->ctx[s], &f, ht_null_first(&sh[s], G->cap), 8);
             null_seen |= f != INF_I64;
         }
         if (S > 1) rfx_hip_ctx_bind_thread(x->ctx[0]);

@@ -297,6 +297,7 @@ static obj_p group_impl(obj_p keys) {
         Q.flags = RFX_Q_WANT_FIRST | RFX_Q_REFUSE_NULL_KEY | RFX_Q_PROBE_FIRST;
         rfx_groups_t R;
         const int grc = rfx_exec_group_by(g_x, &Q, &R);
+        if (grc == RFX_EXEC_NULL_KEY) return fail("group: null keys are not built on the MI355X path"); /* (defensive: the scope pass above refused a null already, no route is known to reach this; the code is positive, no error text goes with it) */
         if (grc != RFX_OK) return fail(rfx_exec_last_error(g_x)[0] ? rfx_exec_last_error(g_x) : rfx_hip_last_error());
         obj_p res_h = NULL;
         void *dg = NULL;
