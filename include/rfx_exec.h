@@ -202,15 +202,25 @@ int rfx_exec_group_median(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_
 int rfx_exec_dev(rfx_exec_t *x, const rfx_query_t *q, const void *d_col, int32_t col_type, rfx_value_t *out);
 int rfx_exec_group_dev(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_t *g, const void *d_col, int32_t col_type, void *d_out);
 
-/* ---- sort (rfx_sort.hip): one shard only (RFX_ELIMIT "sort over a sharded table": a sharded merge sort is its own piece of work) ----
+/* ---- sort (rfx_sort.hip, rfx_merge.hip) ----
  * rfx_exec_sort: d_perm (n i64 cells on shard 0) = the stable lexicographic order of the rows by d_cols[0] (most significant) .. d_cols[ncols-1],
  * all ascending or all descending -- one stable radix sort per column from the last to the first, each reading its keys through the running
  * permutation (core/order.c:266-321,354-409); ties keep ascending row order in both directions.  types[k]: RFX_I64 (also TIMESTAMP) or RFX_F64.
  * rfx_exec_sort_values: d_out = the column's own cells in that order (asc / desc), d_perm (may be NULL) the permutation as well.
  * Rows <= 2^32 - 1; scratch 24 B per row (+ one more permutation of 8 B per row when ncols > 1), freed before return; RFX_ENOMEM when it does not fit.
- * RFX_XSTAT_SORTS / RFX_XSTAT_SORT_PASSES count what ran. */
+ * These two take ONE whole-column address per key, which a sharded context does not have: they refuse it (RFX_ELIMIT "sort over a sharded table").
+ * rfx_exec_sort_shards: the same orders over row-range shards.  cols[k].d[s] is key column k's piece on shard s (rows rfx_exec_split(n, S, s)); every
+ *   shard sorts its piece on its own thread with the kernels above (one key: rfx_hip_sort_values; several: the least-significant-first chain, then
+ *   the key columns gathered into the run's order), runs on another device than shard 0's are copied over (rfx_hip_d2d), runs on shard 0's device are
+ *   read where they lie, and ONE stable multiway merge (rfx_hip_merge_runs) by (key tuple, run, place in run) = (key tuple, global row) writes
+ *   d_perm (n cells) and / or -- ncols == 1 only -- d_values on shard 0's device: the unsharded answer bit for bit.  Either output may be NULL, not
+ *   both.  One shard: the two calls above as they are.  ncols <= RFX_MAX_KEYS over shards, every piece <= 2^32 - 1 rows.  Scratch per shard 16 B per
+ *   row of its piece (one key) or 8 * (ncols + 2) B (several) beside the sort's, + a copy of every cross-device run on shard 0, all freed before return;
+ *   RFX_ENOMEM / RFX_ELIMIT as the sort's; RFX_ELIMIT "sort over several ranks" under a transport or an inter-process communicator.
+ * RFX_XSTAT_SORTS / RFX_XSTAT_SORT_PASSES count what ran, RFX_XSTAT_SORT_MERGES the merges, RFX_XSTAT_NS_SORT_LOCAL / _NS_SORT_MERGE their wall time. */
 int rfx_exec_sort(rfx_exec_t *x, const void *const *d_cols, const int32_t *types, int ncols, int descending, int64_t n, int64_t *d_perm);
 int rfx_exec_sort_values(rfx_exec_t *x, const void *d_col, int32_t type, int descending, int64_t n, void *d_out, int64_t *d_perm);
+int rfx_exec_sort_shards(rfx_exec_t *x, const rfx_qcol_t *cols, const int32_t *types, int ncols, int descending, int64_t n, int64_t *d_perm, void *d_values);
 
 /* ---- join index (index_left_join_obj, core/index.c:2886-2928): d_ids[i] = first right row whose key tuple equals left row i's, else null.
  * RFX_ESTATE with *collision = 1: two key tuples share one 64-bit row hash (nothing may be used).  One shard. */
@@ -385,7 +395,10 @@ enum {
     RFX_XSTAT_ROWS_OUT = 35,      /* ... and rows they answered */
     RFX_XSTAT_CASTS = 36,         /* casts run (one per call or operator piece) */
     RFX_XSTAT_SCOPE_SPARSE_SAMPLED = 37, /* group-bys whose sampled key range alone sent them to the hashed tables (no exact scope pass) */
-    RFX_XSTAT_N = 38
+    RFX_XSTAT_SORT_MERGES = 38,   /* sorts over shards answered by local sorts + one multiway merge (rfx_exec_sort_shards) */
+    RFX_XSTAT_NS_SORT_LOCAL = 39, /* ... wall time of their local-sort phases (to every shard's stream idle), nanoseconds */
+    RFX_XSTAT_NS_SORT_MERGE = 40, /* ... and of the cross-device copies, the merge and the clean-up */
+    RFX_XSTAT_N = 41
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

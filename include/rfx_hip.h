@@ -678,6 +678,31 @@ int rfx_hip_sort_index(rfx_ctx_t *ctx, const void *d_col, int32_t type, int64_t 
 int rfx_hip_sort_values(rfx_ctx_t *ctx, const void *d_col, int32_t type, int64_t n, int descending, void *d_out, int64_t *d_perm_out, int32_t *passes);
 int rfx_hip_inverse_perm(rfx_ctx_t *ctx, const int64_t *d_perm, int64_t n, int64_t *d_out);
 
+/* ---- stable multiway merge of sorted runs (rfx_merge.hip): the second half of a sort over row-range shards ----
+ * Run r is rows [row0, row0 + len) of a table, already sorted by the radix sort above: d_keys[c] = key column c's raw cells in the run's sorted
+ * order (c < nkeys, most significant first), d_rows[p] = the LOCAL row at place p of the run (what rfx_hip_sort_index / _values wrote; NULL when
+ * d_perm_out is not wanted).  The merged order is (sort-key tuple, run, place in run): with runs in row order and stable local sorts that is
+ * (sort-key tuple, global row) -- the unsharded sort's order, bit for bit, in both directions.  Keys are compared through the radix sort's own
+ * sort key computed on the fly from the raw cells (types[c]: RFX_I64 / RFX_F64; one direction for all), so every NaN keeps its sign and payload.
+ * d_perm_out[j] = row0 + d_rows[p] of the record at place j (n = sum of the runs' lengths cells) and / or, with nkeys == 1, d_values_out[j] =
+ * its raw cell.  The keys are read where they lie, once per record plus the binary searches; nothing but the outputs is written.
+ * Launches (no workgroup waits on another): k_merge_splitters -- every `tile`-th record of every run is a splitter; its co-rank in every other
+ * run by binary search (upper bound in earlier runs, lower bound in later ones: the stability), its place = their sum; rfx_hip_sort_index over
+ * the places (distinct); k_merge_segments -- one workgroup per gap between consecutive splitters (at most `tile` records of every run, output
+ * offset = the left splitter's place, exact), every record's place = its own index + its co-ranks inside the other runs' slices, staged through
+ * LDS for a contiguous write-out.  Every search is bounded by its run's len; nothing is read outside a run (len 0 included).
+ * tile: 0 = the shipped one (rfx_hip_merge_tile()), else 512 .. 2048.  nruns <= RFX_MERGE_MAX_RUNS; one run is a copy with row0 added.
+ * Scratch: 8 * (nruns + 2) B per splitter + the sort's over the splitters, rfx_hip_malloc'ed and freed before return (syncs). */
+#define RFX_MERGE_MAX_RUNS 16
+typedef struct rfx_merge_run {
+    const void *d_keys[RFX_MAX_KEYS];
+    const int64_t *d_rows;
+    int64_t len, row0;
+} rfx_merge_run_t;
+int rfx_hip_merge_runs(rfx_ctx_t *ctx, const rfx_merge_run_t *runs, int nruns, const int32_t *types, int nkeys, int descending, int tile,
+                       int64_t *d_perm_out, void *d_values_out);
+int rfx_hip_merge_tile(void);
+
 /* ---- segmented binary search (rfx_asof.hip): asof-join, bin, binr (index_bin_i64 core/index.c:3121-3137, core/items.c:1399-1644) ----
  * The reference's closed-interval loop, step for step -- left = 0, right = len - 1; mid = left + (right - left) / 2 -- because the searched
  * cells need not be sorted and then the probe sequence IS the answer.  right = 0: the last probe position with t[mid] <= q ("<=-last": asof,

@@ -138,6 +138,8 @@ RFX_XSTAT_ROWS_FILTERS, RFX_XSTAT_ROWS_TAKES, RFX_XSTAT_ROWS_REVERSES, RFX_XSTAT
 RFX_Q_ROWS_DIRECT, RFX_Q_ROWS_RING = 64, 128
 RFX_XSTAT_CASTS = 36
 RFX_XSTAT_SCOPE_SPARSE_SAMPLED = 37
+RFX_XSTAT_SORT_MERGES, RFX_XSTAT_NS_SORT_LOCAL, RFX_XSTAT_NS_SORT_MERGE = 38, 39, 40
+RFX_MERGE_MAX_RUNS = 16
 # include/rfx_hip.h RFX_CAST_*: the reference's vector type codes rfx_hip_cast / rfx_exec_cast take
 RFX_CAST = {"b8": 1, "u8": 2, "i16": 3, "i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}
 RFX_CAST_WIDENED = 0x100
@@ -147,6 +149,10 @@ RFX_XRANK_ASC, RFX_XRANK_DESC = 2, 4
 RFX_SET_ROUTE_UNDEFINED, RFX_SET_ROUTE_NONE, RFX_SET_ROUTE_DENSE, RFX_SET_ROUTE_HASH, RFX_SET_ROUTE_DISJOINT, RFX_SET_ROUTE_ATOM = -1, 0, 1, 2, 3, 4
 RFX_WAGG = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "first": 5, "last": 6}  # include/rfx_hip.h RFX_WAGG_*
 RFX_XSTAT_PHASES = (("scope", 9), ("pass", 10), ("merge", 11), ("rank", 12), ("emit", 13), ("fetch", 14), ("total", 15))
+
+
+class MergeRun(C.Structure):  # rfx_merge_run_t
+    _fields_ = [("d_keys", C.c_void_p * RFX_MAX_KEYS), ("d_rows", C.c_void_p), ("len", C.c_int64), ("row0", C.c_int64)]
 
 
 class QCol(C.Structure):
@@ -313,6 +319,8 @@ PROTOTYPES = {
     "rfx_hip_sort_values": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "rfx_hip_inverse_perm": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_xrank": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rfx_hip_merge_runs": (C.c_int, [_ctx, _P(MergeRun), C.c_int, _P(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rfx_hip_merge_tile": (C.c_int, []),
     "rfx_hip_xrank_sorted": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "rfx_hip_xbar": (C.c_int, [_ctx, _P(XbarDesc), C.c_int64, C.c_void_p]),
     "rfx_hip_round_f64": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -399,6 +407,7 @@ EXEC_PROTOTYPES = {
     "rfx_exec_group_dev": (C.c_int, [_exec, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rfx_exec_sort": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_exec_sort_values": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rfx_exec_sort_shards": (C.c_int, [_exec, _P(QCol), _P(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "rfx_exec_xrank": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     "rfx_exec_xbar_plan": (C.c_int, [C.c_int, C.c_int, _P(XbarDesc), _P(C.c_int)]),
     "rfx_exec_xbar": (C.c_int, [_exec, _P(XbarDesc), _P(C.c_void_p), _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),

@@ -66,6 +66,7 @@ struct rfx_exec {
     int no_d2h_pipeline; /* RFX_NO_D2H_PIPELINE=1: large result columns by one plain copy each (A/B) */
     int slice_shards; /* RFX_EXEC_SLICE_SHARDS=1: every SHARD owns a slice of a sliced result, not only every device's lead (how the sharded
                        * tail runs on a one-GPU box: the merged tables are copied to the shards beside their lead first) */
+    int merge_tile;   /* RFX_MERGE_TILE=T: the sharded sort's merge with another splitter tile (measurements; 0 = the shipped one) */
     char err[512];
 };
 static inline int64_t now_ns(void) {

@@ -102,6 +102,8 @@ int rfx_exec_create(rfx_ctx_t *const *ctxs, int nshards, rfx_exec_t **out) {
     x->slice_shards = getenv("RFX_EXEC_SLICE_SHARDS") != NULL;
     x->no_d2h_pipeline = getenv("RFX_NO_D2H_PIPELINE") != NULL;
     x->two_step_rank = getenv("RFX_TWO_STEP_RANK") != NULL;
+    x->merge_tile = getenv("RFX_MERGE_TILE") ? atoi(getenv("RFX_MERGE_TILE")) : 0;
+    if (x->merge_tile < 512 || x->merge_tile > 2048) x->merge_tile = 0; /* (anything the merge does not take: the shipped tile, not a failed sort) */
     for (int s = 0; s < nshards; s++) {
         if (!ctxs[s]) { free(x); return RFX_EINVAL; }
         x->ctx[s] = ctxs[s];

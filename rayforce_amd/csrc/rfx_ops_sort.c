@@ -1,7 +1,10 @@
 /* rfx_ops_sort.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own).
  * iasc / idesc / asc / desc / rank / xasc / xdesc (core/order.c:32-556, core/sort.c:430-479,691-740) over I64 / TIMESTAMP / F64 keys on the device
  * (rfx_sort.hip through rfx_exec_sort); every other shape -- SYMBOL keys (the reference compares strings), LIST / DICT / ENUM, 1/2/4-byte keys,
- * tables holding a column that is not an 8-byte vector, columns spread over shards -- is the host's own verb, the reason in rfx_ops_last_error(). */
+ * tables holding a column that is not an 8-byte vector -- is the host's own verb, the reason in rfx_ops_last_error().
+ * Over shards (RFX_SHARDS=k, RFX_DEVICES=all) the key columns' pieces go through rfx_exec_sort_shards: every shard sorts its rows, one stable multiway
+ * merge on shard 0 (rfx_merge.hip) -- the unsharded answer bit for bit; `rank` inverts the merged permutation there, xasc / xdesc lay every batch of
+ * columns end to end on shard 0's device from their pieces before the gather.  Everything decided before the device is touched is the same. */
 #define ATTR_DISTINCT_ 1
 #define ATTR_ASC_ 2
 #define ATTR_DESC_ 4
@@ -24,6 +27,28 @@ static int sort_tmp(void **d, size_t bytes) {
     if (rc == RFX_OK) g_optmp[g_noptmp++] = *d;
     return rc;
 }
+/* a resident column as the planner's per-shard pieces */
+static int sort_pieces(obj_p c, rfx_qcol_t *q) {
+    const void *d = NULL;
+    int rc = resident(c, 0, &d);
+    if (rc != RFX_OK) return rc;
+    memset(q, 0, sizeof(*q));
+    for (int s = 0; s < g_nshards; s++)
+        if (!(q->d[s] = shard_piece(d, s))) return RFX_ELIMIT;
+    return RFX_OK;
+}
+/* the pieces of a resident column laid end to end at d_whole on shard 0's device (n cells of 8 bytes) */
+static int sort_whole(obj_p c, int64_t n, void *d_whole) {
+    rfx_qcol_t q;
+    int rc = sort_pieces(c, &q);
+    for (int s = 0; s < g_nshards && rc == RFX_OK; s++) {
+        int64_t r0, len;
+        rfx_exec_split(n, g_nshards, s, &r0, &len);
+        if (len > 0) rc = rfx_hip_d2d(g_ctx, (char *)d_whole + (size_t)r0 * 8, q.d[s], (size_t)len * 8);
+    }
+    return rc;
+}
+#define SORT_LIMIT_WHY (g_nshards > 1 ? "a limit of the sort over shards" : "more rows than the device sort takes")
 static int sort_key_type(obj_p c) { return c->type == RFX_TYPE_I64 || c->type == RFX_TYPE_TIMESTAMP || c->type == RFX_TYPE_F64; }
 /* 0..n-1 (attrs ASC | DISTINCT) or n-1..0 (DESC | DISTINCT): the order of a vector whose attribute says it is sorted already */
 static obj_p sort_iota(int64_t n, int down) {
@@ -69,20 +94,23 @@ static obj_p sort_unary(int kind, int f, obj_p x) {
         if (desc ? sorted_up : sorted_down) return sort_iota(n, 1);
     }
     if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
-    if (g_nshards > 1) return sort_host(f, x, NULL, "sort over a sharded table");
     const void *dv = NULL;
     void *d0 = NULL, *d1 = NULL;
-    if (resident(x, 0, &dv) != RFX_OK) return fail_hip("column upload");
+    rfx_qcol_t q;
+    if (g_nshards > 1) {
+        if (sort_pieces(x, &q) != RFX_OK) return fail_hip("column upload");
+    } else if (resident(x, 0, &dv) != RFX_OK) return fail_hip("column upload");
     int rc = sort_tmp(&d0, (size_t)n * 8);
     if (rc == RFX_OK && kind == SORT_RANK) rc = sort_tmp(&d1, (size_t)n * 8);
     if (rc == RFX_OK) {
         const void *cols[1] = {dv};
         const int32_t types[1] = {col_ctype(x)};
-        if (values) rc = rfx_exec_sort_values(g_x, dv, types[0], desc, n, d0, NULL);
+        if (g_nshards > 1) rc = rfx_exec_sort_shards(g_x, &q, types, 1, desc, n, values ? NULL : (int64_t *)d0, values ? d0 : NULL); /* (the outputs on shard 0) */
+        else if (values) rc = rfx_exec_sort_values(g_x, dv, types[0], desc, n, d0, NULL);
         else rc = rfx_exec_sort(g_x, cols, types, 1, desc, n, (int64_t *)d0);
         if (rc == RFX_OK && kind == SORT_RANK) rc = rfx_hip_inverse_perm(g_ctx, (const int64_t *)d0, n, (int64_t *)d1);
     }
-    if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, x, NULL, rc == RFX_ENOMEM ? "device memory" : "more rows than the device sort takes");
+    if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, x, NULL, rc == RFX_ENOMEM ? "device memory" : SORT_LIMIT_WHY);
     if (rc != RFX_OK) return fail_hip("sort");
     obj_p out = H.vector(values ? x->type : RFX_TYPE_I64, n);
     if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), kind == SORT_RANK ? d1 : d0, (size_t)n * 8) != RFX_OK) {
@@ -116,7 +144,7 @@ static obj_p sort_table(int desc, int f, obj_p t, obj_p y) {
         if (!sort_key_type(kc[k])) return sort_host(f, t, y, "key type");
     }
     if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
-    if (g_nshards > 1) return sort_host(f, t, y, "sort over a sharded table");
+    if (g_nshards > 1 && nk > RFX_MAX_KEYS) return sort_host(f, t, y, "more sort columns than a sort over shards takes");
     const void *dperm = NULL;
     obj_p hperm = NULL;
     int on_gpu = 0;
@@ -129,20 +157,23 @@ static obj_p sort_table(int desc, int f, obj_p t, obj_p y) {
         }
     } else if (n > 0) {
         const void *dk[16];
+        rfx_qcol_t qk[RFX_MAX_KEYS];
         int32_t types[16];
         void *d = NULL;
         for (int k = 0; k < nk; k++) {
-            if (resident(kc[k], 0, &dk[k]) != RFX_OK) return fail_hip("column upload");
+            if ((g_nshards > 1 ? sort_pieces(kc[k], &qk[k]) : resident(kc[k], 0, &dk[k])) != RFX_OK) return fail_hip("column upload");
             types[k] = col_ctype(kc[k]);
         }
         int rc = sort_tmp(&d, (size_t)n * 8);
-        if (rc == RFX_OK) rc = rfx_exec_sort(g_x, dk, types, nk, desc, n, (int64_t *)d);
-        if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, t, y, rc == RFX_ENOMEM ? "device memory" : "more rows than the device sort takes");
+        if (rc == RFX_OK) rc = g_nshards > 1 ? rfx_exec_sort_shards(g_x, qk, types, nk, desc, n, (int64_t *)d, NULL) : rfx_exec_sort(g_x, dk, types, nk, desc, n, (int64_t *)d);
+        if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, t, y, rc == RFX_ENOMEM ? "device memory" : SORT_LIMIT_WHY);
         if (rc != RFX_OK) return fail_hip("sort");
         dperm = d;
         on_gpu = 1;
     }
-    /* every column by the final permutation, RFX_MAX_KEYS columns per launch */
+    /* every column by the final permutation, RFX_MAX_KEYS columns per launch; over shards every batch's columns are first laid end to end on shard 0's
+     * device from their pieces (the second half of the batch's block) */
+    const int cat = g_nshards > 1;
     obj_p rv = H.vector(RFX_TYPE_LIST, ncol);
     for (int i = 0; i < ncol; i++) RFX_AS_LIST(rv)[i] = NULL;
     int ok = 1;
@@ -151,10 +182,22 @@ static obj_p sort_table(int desc, int f, obj_p t, obj_p y) {
         const void *src[RFX_MAX_KEYS];
         void *dst[RFX_MAX_KEYS];
         void *block = NULL;
-        ok = rfx_hip_malloc(g_ctx, &block, (size_t)m * (size_t)n * 8) == RFX_OK;
+        const int brc = rfx_hip_malloc(g_ctx, &block, (size_t)m * (size_t)n * 8 * (size_t)(cat ? 2 : 1));
+        if (cat && brc == RFX_ENOMEM) { /* (the whole copies double the batch's block on shard 0: no room is the host's verb, as for the sort's own scratch) */
+            if (hperm) H.drop(hperm);
+            for (int i = 0; i < ncol; i++)
+                if (!RFX_AS_LIST(rv)[i]) RFX_AS_LIST(rv)[i] = H.vector(RFX_AS_LIST(cols)[i]->type, 0);
+            H.drop(rv);
+            return sort_host(f, t, y, "device memory");
+        }
+        ok = brc == RFX_OK;
         for (int j = 0; j < m && ok; j++) {
-            ok = resident(RFX_AS_LIST(cols)[c0 + j], 0, &src[j]) == RFX_OK;
             dst[j] = (char *)block + (size_t)j * (size_t)n * 8;
+            if (cat) {
+                void *whole = (char *)block + (size_t)(m + j) * (size_t)n * 8;
+                ok = sort_whole(RFX_AS_LIST(cols)[c0 + j], n, whole) == RFX_OK;
+                src[j] = whole;
+            } else ok = resident(RFX_AS_LIST(cols)[c0 + j], 0, &src[j]) == RFX_OK;
         }
         ok = ok && rfx_hip_gather_many(g_ctx, src, m, (const int64_t *)dperm, n, dst) == RFX_OK;
         for (int j = 0; j < m && ok; j++) {

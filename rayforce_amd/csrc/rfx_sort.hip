@@ -1,8 +1,7 @@
 // rfx_sort.hip -- stable LSD radix sort of (key, row) pairs: the permutation behind iasc / idesc / rank / xasc / xdesc and the sorted
 // cells behind asc / desc.  gfx950 / wave64.
 //
-// Sort key (core/sort.c:266-285,311 -- the medians' key, rfx_median.hip): i64 x ^ 2^63; f64 NaN -> 0, negative -> ~bits, else bits | 2^63.
-// A descending sort orders by ~key, so ties keep their ascending row order exactly as an ascending sort's do (core/sort.c:584-616).
+// Sort key: sort_key() of rfx_sort_key.hpp, shared with the merge of sorted runs (rfx_merge.hip).
 //
 // Launches (no workgroup ever waits on another inside a launch):
 //   k_sort_keys     the column read once (through perm_in when given) -> the keys, and all eight 8-bit digit histograms (LDS counters per
@@ -18,6 +17,7 @@
 // caller's outputs: the i64 permutation (looked up in perm_in when given) and / or the sorted cells decoded from the keys (a NaN takes its
 // own bits from the column through its row).
 #include "rfx_common.hpp"
+#include "rfx_sort_key.hpp"
 
 #define SORT_THREADS 1024
 #define SORT_WAVES (SORT_THREADS / RFX_WAVE)
@@ -27,14 +27,6 @@
 #define SORT_SMALL_TILE (SORT_THREADS * SORT_SMALL_ITEMS)
 #define SORT_SMALL_ROWS ((i64)1 << 23) /* below: the small tile, so that a few million rows still fill the device */
 #define SORT_MAX_ROWS ((i64)0xFFFFFFFFLL)
-
-__device__ __forceinline__ u64 sort_key(u64 x, int f64, int desc) {
-    u64 k;
-    if (!f64) k = x ^ 0x8000000000000000ULL;
-    else if ((x & 0x7FFFFFFFFFFFFFFFULL) > 0x7FF0000000000000ULL) k = 0ULL; // NaN (either sign, any payload)
-    else k = (x & 0x8000000000000000ULL) ? ~x : (x | 0x8000000000000000ULL);
-    return desc ? ~k : k;
-}
 
 // ---- keys + the eight digit histograms ----
 __global__ __launch_bounds__(RFX_BLOCK) void k_sort_keys(const u64 *__restrict__ col, const i64 *__restrict__ perm_in, i64 n, int f64, int desc,

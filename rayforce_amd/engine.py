@@ -352,9 +352,11 @@ class Engine:
         L.check(self.lib.rfx_hip_gather(self._ctx, col.data_ptr(), ids.data_ptr(), ids.numel(), out.data_ptr()), "gather")
         return out
 
-    def sort_index(self, columns, descending: bool = False) -> torch.Tensor:
+    def sort_index(self, columns, descending: bool = False, over_shards: bool = False) -> torch.Tensor:
         """The stable order of the rows by ``columns`` (one i64 / f64 device column or a sequence, the first most significant; all
-        ascending or all descending) as an i64 device column: iasc / idesc, and the permutation behind xasc / xdesc (rfx_exec_sort)."""
+        ascending or all descending) as an i64 device column: iasc / idesc, and the permutation behind xasc / xdesc (rfx_exec_sort).
+        ``over_shards`` on an engine of several shards: every shard sorts its rows, one stable multiway merge (rfx_exec_sort_shards) -- the
+        same answer bit for bit; without it a sharded engine refuses ("sort over a sharded table")."""
         cols = [columns] if isinstance(columns, torch.Tensor) else list(columns)
         if not cols:
             raise RfxError("sort_index needs at least one column")
@@ -362,17 +364,52 @@ class Engine:
         for c in cols:
             self._check_col(c, n)
         types = (C.c_int32 * len(cols))(*[_ctype_of(c) for c in cols])
-        ptrs = (C.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
         out = torch.empty(n, dtype=torch.int64, device=self.device)
+        if over_shards and self.shards > 1:
+            self._sort_shards(cols, types, descending, n, out.data_ptr(), None)
+            return out
+        ptrs = (C.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
         self._xcheck(self.lib.rfx_exec_sort(self._x, ptrs, types, len(cols), int(bool(descending)), n, out.data_ptr()), "sort")
         return out
 
-    def sort_values(self, col: torch.Tensor, descending: bool = False) -> torch.Tensor:
-        """asc / desc: the column's own cells in sorted order (rfx_exec_sort_values)."""
+    def sort_values(self, col: torch.Tensor, descending: bool = False, over_shards: bool = False) -> torch.Tensor:
+        """asc / desc: the column's own cells in sorted order (rfx_exec_sort_values; ``over_shards`` as for sort_index)."""
         self._check_col(col)
         out = torch.empty_like(col)
+        if over_shards and self.shards > 1:
+            self._sort_shards([col], (C.c_int32 * 1)(_ctype_of(col)), descending, col.numel(), None, out.data_ptr())
+            return out
         self._xcheck(self.lib.rfx_exec_sort_values(self._x, col.data_ptr(), _ctype_of(col), int(bool(descending)), col.numel(), out.data_ptr(), None), "sort")
         return out
+
+    def _sort_shards(self, cols, types, descending, n, d_perm, d_values):
+        qcols = (L.QCol * len(cols))()
+        for k, c in enumerate(cols):
+            pieces = self._pieces(c)
+            for s in range(self.shards):
+                qcols[k].d[s] = pieces[s]
+        self._operands_written()
+        self._xcheck(self.lib.rfx_exec_sort_shards(self._x, qcols, types, len(cols), int(bool(descending)), n, d_perm, d_values), "sort")
+
+    def merge_runs(self, runs, types, descending: bool = False, tile: int = 0, want_perm: bool = True, want_values: bool = False):
+        """The flat merge kernel (rfx_hip_merge_runs): ``runs`` = [(key columns in the run's sorted order, rows or None, row0)], ``types`` the key
+        columns' RFX_I64 / RFX_F64.  Returns (permutation or None, merged cells of the one key column or None)."""
+        arr = (L.MergeRun * len(runs))()
+        n = 0
+        for r, (keys, rows, row0) in enumerate(runs):
+            for k, col in enumerate(keys):
+                arr[r].d_keys[k] = col.data_ptr() if col.numel() else None
+            arr[r].d_rows = rows.data_ptr() if rows is not None and rows.numel() else None
+            arr[r].len = keys[0].numel()
+            arr[r].row0 = int(row0)
+            n += keys[0].numel()
+        perm = torch.empty(n, dtype=torch.int64, device=self.device) if want_perm else None
+        vals = torch.empty(n, dtype=torch.int64, device=self.device) if want_values else None
+        self._operands_written()
+        L.check(self.lib.rfx_hip_merge_runs(self._ctx, arr, len(runs), (C.c_int32 * len(types))(*types), len(types), int(bool(descending)), int(tile),
+                                            perm.data_ptr() if want_perm else None, vals.data_ptr() if want_values else None), "merge_runs")
+        self.sync()
+        return perm, vals
 
     # ------------------------------------------------------------------ bucket verbs (rfx_bucket.hip through rfx_exec_bucket.c)
     _BK_TYPES = {"i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}  # the reference's type codes

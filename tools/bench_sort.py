@@ -5,8 +5,14 @@ keys written --, every executed pass 8 B per row for its count and 24 B per row 
 and that over the time, and the shader clock (hwmon freq1_input, sampled every millisecond).  Two yardsticks in the same run, named for what they are:
 `ref_iasc_ms` the compiled reference's own ray_iasc on this box's CPU (oracle/_ref/librayforce_ref.so, when present) at --ref-rows rows, and
 `torch_sort_ms` torch.sort(stable=True) on the same device tensor (rocPRIM: for information, not in the product).  One JSON line per case.
+--shards k[,k..]: instead, per shard count the sort over k shards of ONE device (rfx_exec_sort_shards: local radix sorts, one multiway merge,
+rfx_merge.hip) beside the unsharded sort of the same column in the same process: the local-sort phase, the merge phase (the planner's own wall-clock
+counters) and the total, and the merge's bytes -- (8 * keys + 8) read and 8 written per row -- over its time against the 8 TB/s roofline.  --tile T
+runs the merge with another splitter tile (RFX_MERGE_TILE; 0 = the shipped one).  Beside the four cases, per shard count one whose runs interleave
+record by record (row mod the shard span): every gap between splitters then holds a tile of every run -- the merge's worst case.
 
     python tools/bench_sort.py [--rows 100000000,1000000000] [--ref-rows 100000000] [--steps 5] [--warmup 1]
+    python tools/bench_sort.py --rows 100000000 --shards 2,4,8 [--tile 2048]
 """
 import argparse
 import ctypes as C
@@ -53,6 +59,46 @@ def reference_iasc_ms(host_i64):
     return best
 
 
+def sharded(a):
+    if a.tile:
+        os.environ["RFX_MERGE_TILE"] = str(a.tile)  # (read when a planner is created)
+    eng = Engine(0)
+    tile = a.tile or eng.lib.rfx_hip_merge_tile()
+    g = torch.Generator(device=eng.device).manual_seed(1)
+    for n in [int(x) for x in a.rows.split(",")]:
+        narrow = torch.randint(0, 1_000_000, (n,), dtype=torch.int64, device=eng.device, generator=g)
+        second = torch.randint(0, 1000, (n,), dtype=torch.int64, device=eng.device, generator=g)
+        full = torch.randint(-(1 << 62), 1 << 62, (n,), dtype=torch.int64, device=eng.device, generator=g)
+        f = torch.rand(n, dtype=torch.float64, device=eng.device, generator=g)
+        cases = [("iasc i64 [0,1e6)", [narrow]), ("iasc i64 full range", [full]), ("iasc f64 uniform", [f]), ("xasc by two columns ([0,1e3) then [0,1e6))", [second, narrow])]
+        one = {}
+        for case, cols in cases:
+            one[case], _ = timed(lambda: eng.sort_index(cols), a.steps, a.warmup, None)
+            print(json.dumps({"case": case, "rows": n, "shards": 1, "ms": round(one[case], 3), "steps": a.steps}), flush=True)
+        for k in [int(x) for x in a.shards.split(",")]:
+            es = Engine(0, shards=k)
+            # the merge's worst case: every shard holds the same keys 0 .. span-1, so every gap between splitters holds a tile of EVERY run
+            span = ((n + k - 1) // k + 511) & ~511
+            inter = torch.arange(n, dtype=torch.int64, device=eng.device) % span
+            name = "iasc i64 interleaved runs (row mod the shard span)"
+            one[name], _ = timed(lambda: eng.sort_index([inter]), a.steps, a.warmup, None)
+            for case, cols in cases + [(name, [inter])]:
+                for _ in range(a.warmup):
+                    es.sort_index(cols, over_shards=True)
+                before = [es.xstat(s) for s in (L.RFX_XSTAT_NS_SORT_LOCAL, L.RFX_XSTAT_NS_SORT_MERGE)]
+                ms, _ = timed(lambda: es.sort_index(cols, over_shards=True), a.steps, 0, None)
+                local, merge = [(es.xstat(s) - b) / a.steps / 1e6 for s, b in zip((L.RFX_XSTAT_NS_SORT_LOCAL, L.RFX_XSTAT_NS_SORT_MERGE), before)]
+                moved = n * (8 * len(cols) + 8 + 8)
+                print(json.dumps({"case": case, "rows": n, "shards": k, "tile": tile, "ms": round(ms, 3), "local_sort_ms_mean": round(local, 3),
+                                  "merge_ms_mean": round(merge, 3), "merge_model_gb": round(moved / 1e9, 2), "merge_tb_s": round(moved / merge / 1e9, 3),
+                                  "merge_of_8tb_s_roofline": round(moved / merge / 1e9 / 8.0, 3), "one_shard_ms": round(one[case], 3),
+                                  "over_one_shard": round(ms / one[case], 2), "steps": a.steps}), flush=True)
+            es.close()
+        del narrow, second, full, f
+        torch.cuda.empty_cache()
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="100000000,1000000000")
@@ -60,7 +106,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--shards", default="")
+    ap.add_argument("--tile", type=int, default=0)
     a = ap.parse_args()
+    if a.shards:
+        return sharded(a)
     eng = Engine(0)
     clock = hwmon(eng.device.index)
     g = torch.Generator(device=eng.device).manual_seed(1)
