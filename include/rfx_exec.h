@@ -205,16 +205,22 @@ int rfx_exec_group_dev(rfx_exec_t *x, const rfx_query_t *q, const rfx_groups_t *
 /* ---- sort (rfx_sort.hip, rfx_merge.hip) ----
  * rfx_exec_sort: d_perm (n i64 cells on shard 0) = the stable lexicographic order of the rows by d_cols[0] (most significant) .. d_cols[ncols-1],
  * all ascending or all descending -- one stable radix sort per column from the last to the first, each reading its keys through the running
- * permutation (core/order.c:266-321,354-409); ties keep ascending row order in both directions.  types[k]: RFX_I64 (also TIMESTAMP) or RFX_F64.
- * rfx_exec_sort_values: d_out = the column's own cells in that order (asc / desc), d_perm (may be NULL) the permutation as well.
- * Rows <= 2^32 - 1; scratch 24 B per row (+ one more permutation of 8 B per row when ncols > 1), freed before return; RFX_ENOMEM when it does not fit.
+ * permutation (core/order.c:266-321,354-409); ties keep ascending row order in both directions.  types[k]: RFX_I64 (also TIMESTAMP), RFX_F64, or a
+ * key of at most 32 bits as rfx_hip_sort_index takes it -- RFX_I32 (raw 4-byte cells; DATE / TIME too), RFX_I32_WIDE (their widened 8-byte image),
+ * RFX_I16, RFX_U8, RFX_B8; the columns of one call may mix them: every level picks its record form by its column's type.
+ * rfx_exec_sort_values: d_out = the column's own cells in that order (asc / desc) IN THE COLUMN'S OWN WIDTH (4-byte cells from RFX_I32_WIDE too),
+ * d_perm (may be NULL) the permutation as well.
+ * Rows <= 2^32 - 1; scratch 24 B per row for an 8-byte key, 16 B for a narrower one (+ one more permutation of 8 B per row when ncols > 1), freed
+ * before return; RFX_ENOMEM when it does not fit.
  * These two take ONE whole-column address per key, which a sharded context does not have: they refuse it (RFX_ELIMIT "sort over a sharded table").
  * rfx_exec_sort_shards: the same orders over row-range shards.  cols[k].d[s] is key column k's piece on shard s (rows rfx_exec_split(n, S, s)); every
  *   shard sorts its piece on its own thread with the kernels above (one key: rfx_hip_sort_values; several: the least-significant-first chain, then
  *   the key columns gathered into the run's order), runs on another device than shard 0's are copied over (rfx_hip_d2d), runs on shard 0's device are
  *   read where they lie, and ONE stable multiway merge (rfx_hip_merge_runs) by (key tuple, run, place in run) = (key tuple, global row) writes
  *   d_perm (n cells) and / or -- ncols == 1 only -- d_values on shard 0's device: the unsharded answer bit for bit.  Either output may be NULL, not
- *   both.  One shard: the two calls above as they are.  ncols <= RFX_MAX_KEYS over shards, every piece <= 2^32 - 1 rows.  Scratch per shard 16 B per
+ *   both.  types[k]: RFX_I64 / RFX_F64 ONLY -- an I32-family column is given as its widened pieces under RFX_I64 (order and nulls survive the
+ *   widening; the caller narrows merged cells), 1- and 2-byte keys are not taken.  One shard: the two calls above as they are.  ncols <=
+ *   RFX_MAX_KEYS over shards, every piece <= 2^32 - 1 rows.  Scratch per shard 16 B per
  *   row of its piece (one key) or 8 * (ncols + 2) B (several) beside the sort's, + a copy of every cross-device run on shard 0, all freed before return;
  *   RFX_ENOMEM / RFX_ELIMIT as the sort's; RFX_ELIMIT "sort over several ranks" under a transport or an inter-process communicator.
  * RFX_XSTAT_SORTS / RFX_XSTAT_SORT_PASSES count what ran, RFX_XSTAT_SORT_MERGES the merges, RFX_XSTAT_NS_SORT_LOCAL / _NS_SORT_MERGE their wall time. */

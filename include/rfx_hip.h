@@ -49,7 +49,7 @@ enum {
 };
 
 /* ---- element types: same numbers as the reference's vector type codes (include/rfx_abi.h) ---- */
-enum { RFX_B8 = 1, RFX_I64 = 5, RFX_F64 = 10 };
+enum { RFX_B8 = 1, RFX_U8 = 2, RFX_I16 = 3, RFX_I64 = 5, RFX_F64 = 10 }; /* (RFX_I32 = 4 and its widened form RFX_I32_WIDE: below, beside rfx_hip_neg) */
 
 /* ---- comparison operators: ray_eq .. ray_ge (core/cmp.c:692-697), scalar rules core/ops.h:76-123 ---- */
 enum { RFX_EQ = 0, RFX_NE = 1, RFX_LT = 2, RFX_GT = 3, RFX_LE = 4, RFX_GE = 5 };
@@ -664,10 +664,17 @@ int rfx_hip_median_keys(rfx_ctx_t *ctx, const void *d_val, int32_t val_type, int
 
 /* ---- stable radix sort (rfx_sort.hip): the order behind iasc / idesc / asc / desc / rank / xasc / xdesc (core/sort.c, core/order.c) ----
  * Rows are ordered by the medians' sort key u(x) above (descending: by ~u(x)); equal keys keep their ascending row order in BOTH directions.
- * So nulls (NULL_I64, any NaN) come first ascending and last descending, -0.0 < +0.0.  type: RFX_I64 (also TIMESTAMP) or RFX_F64.
- * An LSD radix sort over 8-bit digits of (u64 key, u32 row) records; a digit on which every key agrees costs no pass (*passes, may be NULL,
- * receives the number that ran: 0..8).  n <= 2^32 - 1 rows (RFX_ELIMIT above).  Scratch: 24 B per row + 1 KB per tile of 16384 rows (2048
- * below 2^23 rows), rfx_hip_malloc'ed and freed before return (syncs); RFX_ENOMEM when the device cannot hold it.
+ * So nulls (NULL_I64, any NaN) come first ascending and last descending, -0.0 < +0.0.
+ * type, 8-byte keys: RFX_I64 (also TIMESTAMP) or RFX_F64.  An LSD radix sort over 8-bit digits of (u64 key, u32 row) records; a digit on which
+ *   every key agrees costs no pass (*passes, may be NULL, receives the number that ran: 0..8).  Scratch: 24 B per row.
+ * type, keys of at most 32 bits: RFX_I32 (raw 4-byte cells; also DATE / TIME), RFX_I32_WIDE (the same cells held as their widened 8-byte image,
+ *   rfx_hip_widen_i32), RFX_I16 (2-byte cells), RFX_U8 and RFX_B8 (1-byte cells, ordered as unsigned bytes).  The 32-bit key: the byte itself;
+ *   (u16)x ^ 0x8000; (u32)x ^ 0x80000000 (so INT32_MIN, the null, is 0: first ascending, last descending); of the widened image NULL_I64 -> 0, else
+ *   the low 32 bits ^ 0x80000000.  Descending orders by the complement within the key's width.  ONE u64 record per row, key << 32 | row, in one
+ *   ping-pong pair; passes 0..4 (I32), 0..2 (I16), 0..1 (U8 / B8).  Scratch: 16 B per row.  Sorted cells (rfx_hip_sort_values) leave in the
+ *   column's OWN width -- 4-, 2- or 1-byte cells, from the widened image too -- decoded from the key alone.
+ * n <= 2^32 - 1 rows (RFX_ELIMIT above).  Scratch besides the records: 1 KB per tile of 8192 rows (2048 below 2^23 rows) + the histograms,
+ * rfx_hip_malloc'ed and freed before return (syncs); RFX_ENOMEM when the device cannot hold it.  d_col, d_out 16-byte aligned.
  * rfx_hip_sort_index: d_perm_out[j] = the row at place j.  With d_perm_in (one level of a multi-column sort) the keys are read through it --
  *   u(d_col[d_perm_in[i]]) -- and d_perm_out[j] = d_perm_in[src(j)]; d_perm_in == NULL is 0..n-1.  d_perm_out may not alias d_perm_in.
  * rfx_hip_sort_values: d_out[j] = the ORIGINAL cell at place j (decoded from the key; a NaN takes its own sign and payload from the column
@@ -801,7 +808,7 @@ int rfx_hip_set_compact(rfx_ctx_t *ctx, const uint64_t *d_flags, int64_t nbits, 
  *   stays the null), RFX_F64 -> the sign bit flipped (NaNs too).
  * rfx_hip_within_i64: d_mask[i] = lo <= d_col[i] && d_col[i] <= hi as 0 / 1 bytes (ray_within, core/items.c:863-872: plain signed compares, a null
  *   cell is the smallest value); d_col 16-byte, d_mask 8-byte aligned. */
-enum { RFX_I32 = 4, RFX_I32_WIDE = 0x104 }; /* (_WIDE: rfx_hip_neg alone) */
+enum { RFX_I32 = 4, RFX_I32_WIDE = 0x104 }; /* (_WIDE: rfx_hip_neg and the sort) */
 enum { RFX_ROUND_FLOOR = 0, RFX_ROUND_CEIL = 1, RFX_ROUND_ROUND = 2 };
 typedef struct rfx_xbar_desc {
     const void *d_x, *d_y;

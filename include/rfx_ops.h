@@ -32,8 +32,8 @@
  *   rfx_add rfx_sub        ray_add ray_sub       core/math.c:2280-2345 (binop_map)   binary_f  vector (x) vector | atom -> vector
  *   rfx_mul rfx_div        ray_mul ray_fdiv (`div`)                                  binary_f  (i64 / f64, the reference's promotion)
  *   rfx_floordiv rfx_mod   ray_div (`/`: floor division, left operand's type) ray_mod (`%`)   binary_f  (core/math.c:1138-1364, 1449-1530)
- *   rfx_iasc rfx_idesc     ray_iasc ray_idesc    core/order.c:32-72              unary_f   I64 / TIMESTAMP / F64 vector -> I64 permutation
- *   rfx_asc rfx_desc       ray_asc ray_desc      core/order.c:74-244             unary_f   -> the sorted cells, ATTR_ASC / ATTR_DESC
+ *   rfx_iasc rfx_idesc     ray_iasc ray_idesc    core/order.c:32-72              unary_f   I64 / TIMESTAMP / F64 / I32 / DATE / TIME / I16 / U8 / B8 vector -> I64 permutation
+ *   rfx_asc rfx_desc       ray_asc ray_desc      core/order.c:74-244             unary_f   -> the sorted cells in the vector's own type, ATTR_ASC / ATTR_DESC
  *   rfx_rank               ray_rank              core/order.c:519-556            unary_f   -> the inverse of iasc
  *   rfx_xasc rfx_xdesc     ray_xasc ray_xdesc    core/order.c:246-420            binary_f  (table, column symbol | symbol vector) -> table
  *   rfx_asof_join          ray_asof_join         core/join.c:300-356             vary_f    (key symbols, the last one the asof column; left table, right table)
@@ -142,11 +142,14 @@ rfx_obj_p rfx_dev(rfx_obj_p x);
 /* ray_med (core/math.c:2529-2626): an I64 vector, a MAPFILTER over one, or a MAPGROUP (IDS / SHIFT index, with or without filter ids) over I64 /
  * TIMESTAMP / F64 values -> the exact median(s) as F64 (rfx_median.hip); every other argument is the host's ray_med */
 rfx_obj_p rfx_med(rfx_obj_p x);
-/* ray_iasc / ray_idesc / ray_asc / ray_desc / ray_rank (core/order.c:32-244,519-556) of an I64 / TIMESTAMP / F64 vector, ray_xasc / ray_xdesc
+/* ray_iasc / ray_idesc / ray_asc / ray_desc / ray_rank (core/order.c:32-244,519-556) of an I64 / TIMESTAMP / F64 vector, or of an I32 / DATE /
+ * TIME / I16 / U8 / B8 one (core/sort.c:183-263,481-559: by signed value, B8 / U8 by the unsigned byte; INT32_MIN is the null); ray_xasc / ray_xdesc
  * (core/order.c:246-420) of a table of 8-byte columns by one symbol or a symbol vector of I64 / TIMESTAMP / F64 columns: a stable radix sort on the
  * device (rfx_sort.hip).  Nulls first ascending, last descending; ties in ascending row order in both directions; asc / desc return the original
- * cells with ATTR_ASC / ATTR_DESC (| the argument's ATTR_DISTINCT); an argument carrying ATTR_ASC / ATTR_DESC is answered from the attribute as the
- * reference does.  Every other shape (SYMBOL / LIST / DICT / ENUM / 1-2-4-byte keys, other column types, sharded columns) is the host's own verb. */
+ * cells in the argument's type with ATTR_ASC / ATTR_DESC (| the argument's ATTR_DISTINCT); an argument carrying ATTR_ASC / ATTR_DESC is answered
+ * from the attribute as the reference does (an I16 vector whose attribute asks asc / desc for a reverse is the host's: its ray_reverse has no I16
+ * arm).  Every other shape (SYMBOL / C8 / LIST / DICT / ENUM keys, tables holding 1-2-4-byte columns, 1- and 2-byte keys over shards) is the
+ * host's own verb. */
 rfx_obj_p rfx_iasc(rfx_obj_p x);
 rfx_obj_p rfx_idesc(rfx_obj_p x);
 rfx_obj_p rfx_asc(rfx_obj_p x);

@@ -9,6 +9,7 @@ RFX_ELIMIT = -5
 RFX_ESTATE = -6
 RFX_B8, RFX_I64, RFX_F64 = 1, 5, 10
 RFX_I32 = 4  # element storage of the bucket verbs' 4-byte operands (I32 / DATE / TIME)
+RFX_U8, RFX_I16, RFX_I32_WIDE = 2, 3, 0x104  # the sort's other narrow key types; _WIDE: 4-byte cells held as their widened 8-byte image
 RFX_ROUND_FLOOR, RFX_ROUND_CEIL, RFX_ROUND_ROUND = 0, 1, 2
 RFX_EQ, RFX_NE, RFX_LT, RFX_GT, RFX_LE, RFX_GE = range(6)
 RFX_AND, RFX_OR = 0, 1

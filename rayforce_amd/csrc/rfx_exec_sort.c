@@ -1,7 +1,13 @@
 /* rfx_exec_sort.c -- part of the planner's ONE translation unit (rfx_exec.c #includes it -- the Makefile does not compile it on its own).
  * The sorts behind iasc / idesc / asc / desc / rank / xasc / xdesc: which columns, in which order, through which permutation; the kernels of
- * rfx_sort.hip decide per column which of the eight digit passes move anything.  rfx_exec_sort / _sort_values: one shard, whole-column addresses;
- * rfx_exec_sort_shards (at the end): per-shard pieces, local sorts on the shards' threads, one merge on shard 0 (rfx_merge.hip). */
+ * rfx_sort.hip decide per column which of the digit passes move anything, and by the column's type which record form runs (8-byte keys: u64 key +
+ * u32 row; keys of at most 32 bits: one packed u64), so the levels of a multi-column sort may mix widths.  rfx_exec_sort / _sort_values: one shard,
+ * whole-column addresses; rfx_exec_sort_shards (at the end): per-shard pieces of 8-byte keys only, local sorts on the shards' threads, one merge on
+ * shard 0 (rfx_merge.hip). */
+static int sort_type_ok(int32_t t) {
+    return t == RFX_I64 || t == RFX_F64 || t == RFX_I32 || t == RFX_I32_WIDE || t == RFX_I16 || t == RFX_U8 || t == RFX_B8;
+}
+#define SORT_TYPES_WHY "rfx_exec: sort keys are i64 / timestamp / f64 columns, or i32 / date / time (raw or widened), i16, u8 and b8 ones on one shard"
 static int sort_one_shard(rfx_exec_t *x) {
     if (x->nshards > 1 || x->has_tr) {
         snprintf(x->err, sizeof(x->err), "rfx_exec: sort over a sharded table");
@@ -15,8 +21,8 @@ int rfx_exec_sort(rfx_exec_t *x, const void *const *d_cols, const int32_t *types
     int rc = sort_one_shard(x);
     if (rc != RFX_OK) return rc;
     for (int k = 0; k < ncols; k++)
-        if ((types[k] != RFX_I64 && types[k] != RFX_F64) || (n > 0 && !d_cols[k])) {
-            snprintf(x->err, sizeof(x->err), "rfx_exec: sort keys are i64 / timestamp / f64 columns");
+        if (!sort_type_ok(types[k]) || (n > 0 && !d_cols[k])) {
+            snprintf(x->err, sizeof(x->err), SORT_TYPES_WHY);
             return RFX_EINVAL;
         }
     if (n == 0) return RFX_OK;
@@ -51,8 +57,8 @@ int rfx_exec_sort_values(rfx_exec_t *x, const void *d_col, int32_t type, int des
     x->err[0] = 0;
     int rc = sort_one_shard(x);
     if (rc != RFX_OK) return rc;
-    if (type != RFX_I64 && type != RFX_F64) {
-        snprintf(x->err, sizeof(x->err), "rfx_exec: sort keys are i64 / timestamp / f64 columns");
+    if (!sort_type_ok(type)) {
+        snprintf(x->err, sizeof(x->err), SORT_TYPES_WHY);
         return RFX_EINVAL;
     }
     if (n == 0) return RFX_OK;
@@ -131,8 +137,8 @@ int rfx_exec_sort_shards(rfx_exec_t *x, const rfx_qcol_t *cols, const int32_t *t
     if (!x || !cols || !types || ncols < 1 || n < 0 || (n > 0 && !d_perm && !d_values) || (d_values && ncols != 1)) return RFX_EINVAL;
     x->err[0] = 0;
     for (int k = 0; k < ncols; k++)
-        if ((types[k] != RFX_I64 && types[k] != RFX_F64) || (n > 0 && !cols[k].d[0])) {
-            snprintf(x->err, sizeof(x->err), "rfx_exec: sort keys are i64 / timestamp / f64 columns");
+        if ((types[k] != RFX_I64 && types[k] != RFX_F64) || (n > 0 && !cols[k].d[0])) { /* (an I32-family column comes as its widened pieces, RFX_I64) */
+            snprintf(x->err, sizeof(x->err), SORT_TYPES_WHY);
             return RFX_EINVAL;
         }
     if (x->has_tr || rfx_exec_ranks(x, NULL) > 1) {

@@ -1,10 +1,14 @@
 /* rfx_ops_sort.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own).
  * iasc / idesc / asc / desc / rank / xasc / xdesc (core/order.c:32-556, core/sort.c:430-479,691-740) over I64 / TIMESTAMP / F64 keys on the device
- * (rfx_sort.hip through rfx_exec_sort); every other shape -- SYMBOL keys (the reference compares strings), LIST / DICT / ENUM, 1/2/4-byte keys,
- * tables holding a column that is not an 8-byte vector -- is the host's own verb, the reason in rfx_ops_last_error().
+ * (rfx_sort.hip through rfx_exec_sort).  The five vector verbs also take I32 / DATE / TIME (the resident widened copy, RFX_I32_WIDE), B8 (the
+ * resident 1-byte copy; B8 device-column handles too) and I16 / U8 (raw cells uploaded for the call only) -- the sort's packed-record path; asc /
+ * desc answer cells of x's own width.  Every other shape -- SYMBOL keys (the reference picks id order or string order), C8, LIST / DICT / ENUM,
+ * tables holding a column that is not an 8-byte vector, 4-byte xrank keys -- is the host's own verb, the reason in rfx_ops_last_error().
  * Over shards (RFX_SHARDS=k, RFX_DEVICES=all) the key columns' pieces go through rfx_exec_sort_shards: every shard sorts its rows, one stable multiway
  * merge on shard 0 (rfx_merge.hip) -- the unsharded answer bit for bit; `rank` inverts the merged permutation there, xasc / xdesc lay every batch of
- * columns end to end on shard 0's device from their pieces before the gather.  Everything decided before the device is touched is the same. */
+ * columns end to end on shard 0's device from their pieces before the gather.  Everything decided before the device is touched is the same.
+ * An I32-family vector goes over shards as its widened pieces under RFX_I64 (order and nulls survive the widening); asc / desc narrow the merged
+ * 8-byte cells on shard 0 with rfx_hip_rows_take's RFX_ROWS_4W form before they leave.  I16 / U8 / B8 keys over shards are the host's verb. */
 #define ATTR_DISTINCT_ 1
 #define ATTR_ASC_ 2
 #define ATTR_DESC_ 4
@@ -57,16 +61,32 @@ static obj_p sort_iota(int64_t n, int down) {
     o->attrs = (uint8_t)((down ? ATTR_DESC_ : ATTR_ASC_) | ATTR_DISTINCT_);
     return o;
 }
+/* bytes of one cell of a vector type the vector verbs take (0: another type) */
+static size_t sort_cell_bytes(int type) {
+    switch (type) {
+        case RFX_TYPE_B8: case RFX_TYPE_U8: return 1;
+        case RFX_TYPE_I16: return 2;
+        case RFX_TYPE_I32: case RFX_TYPE_DATE: case RFX_TYPE_TIME: return 4;
+        case RFX_TYPE_I64: case RFX_TYPE_TIMESTAMP: case RFX_TYPE_F64: return 8;
+        default: return 0;
+    }
+}
 static obj_p sort_reversed(obj_p x) { /* ray_reverse (core/compose.c:144-202): ATTR_ASC and ATTR_DESC change places, the other attributes stay */
     obj_p o = H.vector(x->type, x->len);
-    for (int64_t i = 0; i < x->len; i++) RFX_AS_I64(o)[i] = RFX_AS_I64(x)[x->len - 1 - i];
+    const size_t w = sort_cell_bytes(x->type);
+    const char *src = (const char *)RFX_AS_RAW(x);
+    char *dst = (char *)RFX_AS_RAW(o);
+    for (int64_t i = 0; i < x->len; i++) memcpy(dst + (size_t)i * w, src + (size_t)(x->len - 1 - i) * w, w);
     o->attrs = (uint8_t)((x->attrs & ~(ATTR_ASC_ | ATTR_DESC_)) | ((x->attrs & ATTR_ASC_) ? ATTR_DESC_ : 0) | ((x->attrs & ATTR_DESC_) ? ATTR_ASC_ : 0));
     return o;
 }
 static obj_p sort_unary(int kind, int f, obj_p x) {
     rfx_host_bind();
     if (!x) return fail("sort: null argument");
-    if (!(x->type > 0 && sort_key_type(x))) return sort_host(f, x, NULL, "key type");
+    const size_t w = x->type > 0 ? sort_cell_bytes(x->type) : 0; /* (SYMBOL, C8, LIST ...: 0) */
+    if (!w) return sort_host(f, x, NULL, "key type");
+    const int wide = w == 8, i32 = IS_I32_FAMILY(x->type);
+    if (x->mmod == RFX_MMOD_DEVICE && !wide && x->type != RFX_TYPE_B8) return sort_host(f, x, NULL, "a device column that is not I64 / F64 / TIMESTAMP / B8");
     const int64_t n = x->len;
     const int desc = kind == SORT_IDESC || kind == SORT_DESC, values = kind == SORT_ASC || kind == SORT_DESC;
     const int sorted_up = x->attrs & ATTR_ASC_, sorted_down = x->attrs & ATTR_DESC_;
@@ -75,7 +95,10 @@ static obj_p sort_unary(int kind, int f, obj_p x) {
     /* the attribute is trusted, not the data (core/sort.c:430-451,691-712; core/order.c:79-83,165-169,524-538) */
     if (values) {
         if (desc ? sorted_down : sorted_up) return H.clone(x);
-        if (desc ? sorted_up : sorted_down) return sort_reversed(x);
+        if (desc ? sorted_up : sorted_down) {
+            if (x->type == RFX_TYPE_I16) return sort_host(f, x, NULL, "the reference's reverse has no I16 arm"); /* (its err_type, core/compose.c:195-196) */
+            return sort_reversed(x);
+        }
     } else if (kind == SORT_RANK) {
         if (sorted_up) return sort_iota(n, 0); /* (ray_til: attrs ASC | DISTINCT) */
         if (sorted_down) {
@@ -94,26 +117,43 @@ static obj_p sort_unary(int kind, int f, obj_p x) {
         if (desc ? sorted_up : sorted_down) return sort_iota(n, 1);
     }
     if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
+    if (g_nshards > 1 && !wide && !i32) return sort_host(f, x, NULL, "1- and 2-byte keys over shards");
     const void *dv = NULL;
     void *d0 = NULL, *d1 = NULL;
     rfx_qcol_t q;
-    if (g_nshards > 1) {
-        if (sort_pieces(x, &q) != RFX_OK) return fail_hip("column upload");
-    } else if (resident(x, 0, &dv) != RFX_OK) return fail_hip("column upload");
-    int rc = sort_tmp(&d0, (size_t)n * 8);
-    if (rc == RFX_OK && kind == SORT_RANK) rc = sort_tmp(&d1, (size_t)n * 8);
+    int rc = RFX_OK;
+    int32_t type; /* as the planner takes it */
+    if (x->type == RFX_TYPE_I16 || x->type == RFX_TYPE_U8) { /* (the residency cache keeps 8-byte, widened 4-byte and B8 columns: raw cells for this call only) */
+        void *raw = NULL;
+        rc = sort_tmp(&raw, (size_t)n * w);
+        if (rc == RFX_OK && rfx_hip_h2d_pipelined(g_ctx, raw, RFX_AS_RAW(x), (size_t)n * w) != RFX_OK) return fail_hip("column upload");
+        if (rc == RFX_OK) g_stat[ST_UPLOADS]++;
+        dv = raw;
+        type = x->type == RFX_TYPE_I16 ? RFX_I16 : RFX_U8;
+    } else {
+        if (g_nshards > 1) {
+            if (sort_pieces(x, &q) != RFX_OK) return fail_hip("column upload");
+        } else if (resident(x, 0, &dv) != RFX_OK) return fail_hip("column upload");
+        /* (the resident copy of a 4-byte column is its widened image; over shards its pieces sort and merge as the 8-byte integers they are) */
+        type = i32 ? (g_nshards > 1 ? RFX_I64 : RFX_I32_WIDE) : x->type == RFX_TYPE_B8 ? RFX_B8 : col_ctype(x);
+    }
+    const size_t ow = values ? w : 8; /* bytes of one cell of the answer */
+    if (rc == RFX_OK) rc = sort_tmp(&d0, (size_t)n * 8);
+    if (rc == RFX_OK && (kind == SORT_RANK || (values && i32 && g_nshards > 1))) rc = sort_tmp(&d1, (size_t)n * 8);
+    const void *d_res = d0;
     if (rc == RFX_OK) {
         const void *cols[1] = {dv};
-        const int32_t types[1] = {col_ctype(x)};
+        const int32_t types[1] = {type};
         if (g_nshards > 1) rc = rfx_exec_sort_shards(g_x, &q, types, 1, desc, n, values ? NULL : (int64_t *)d0, values ? d0 : NULL); /* (the outputs on shard 0) */
         else if (values) rc = rfx_exec_sort_values(g_x, dv, types[0], desc, n, d0, NULL);
         else rc = rfx_exec_sort(g_x, cols, types, 1, desc, n, (int64_t *)d0);
-        if (rc == RFX_OK && kind == SORT_RANK) rc = rfx_hip_inverse_perm(g_ctx, (const int64_t *)d0, n, (int64_t *)d1);
+        if (rc == RFX_OK && kind == SORT_RANK) rc = rfx_hip_inverse_perm(g_ctx, (const int64_t *)d0, n, (int64_t *)d1), d_res = d1;
+        else if (rc == RFX_OK && d1) rc = rfx_hip_rows_take(g_ctx, d0, RFX_ROWS_4W, n, 0, n, d1), d_res = d1; /* (the merged 8-byte cells -> 4-byte cells) */
     }
     if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, x, NULL, rc == RFX_ENOMEM ? "device memory" : SORT_LIMIT_WHY);
     if (rc != RFX_OK) return fail_hip("sort");
     obj_p out = H.vector(values ? x->type : RFX_TYPE_I64, n);
-    if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), kind == SORT_RANK ? d1 : d0, (size_t)n * 8) != RFX_OK) {
+    if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), d_res, (size_t)n * ow) != RFX_OK) {
         H.drop(out);
         return fail_hip("sort result");
     }

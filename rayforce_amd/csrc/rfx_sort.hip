@@ -16,6 +16,12 @@
 // Records are a u64 key and a u32 row (rows < 2^32), in two ping-pong pairs; the first pass reads rows as 0..n-1 and the last one writes the
 // caller's outputs: the i64 permutation (looked up in perm_in when given) and / or the sorted cells decoded from the keys (a NaN takes its
 // own bits from the column through its row).
+//
+// Keys of at most 32 bits (B8 / U8, I16, I32 / DATE / TIME as raw cells or as the widened 8-byte image; sort_key32() of rfx_sort_key.hpp) travel as
+// ONE u64 record, key << 32 | row, in one ping-pong pair: k_sort_keys32 builds the records and only the 1, 2 or 4 histograms the key's width has,
+// a pass streams 8 B per row in and out instead of 12, and the last pass decodes the sorted cells in the column's own width from the key alone.
+// The digit of a pass sits at bit 32 + 8 d of the record, so k_sort_count and k_sort_scan run as they are; k_sort_scatter is one template over the
+// record form.
 #include "rfx_common.hpp"
 #include "rfx_sort_key.hpp"
 
@@ -56,6 +62,72 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_sort_keys(const u64 *__restrict__
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 8 * 256; i += RFX_BLOCK)
+        if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
+}
+
+// ---- packed records + the histograms of a key of at most 32 bits ----
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+// one cell's digits into the workgroup's histograms; a digit the whole wave agrees on is one add, as above
+template <int NDIG> __device__ __forceinline__ void sort_hist32(unsigned int *lh, unsigned int k, int lane) {
+#pragma unroll
+    for (int d = 0; d < NDIG; d++) {
+        const int dg = (int)((k >> (8 * d)) & 255), first = __builtin_amdgcn_readfirstlane(dg);
+        const u64 active = __ballot(1);
+        if (__ballot(dg == first) == active) {
+            if (lane == __ffsll((long long)active) - 1) atomicAdd(&lh[d * 256 + first], (unsigned int)__popcll(active));
+        } else atomicAdd(&lh[d * 256 + dg], 1u);
+    }
+}
+template <int CLS> __device__ __forceinline__ u64 sort_ld32(const void *p, i64 r) {
+    if (CLS == SK_U8) return ((const unsigned char *)p)[r];
+    if (CLS == SK_I16) return ((const unsigned short *)p)[r];
+    if (CLS == SK_I32) return ((const unsigned int *)p)[r];
+    return ((const u64 *)p)[r];
+}
+// cell j of a lane's 16 bytes
+template <int CLS> __device__ __forceinline__ u64 sort_pick32(const unsigned int *w, int j) {
+    if (CLS == SK_U8) return (w[j / 4] >> (8 * (j % 4))) & 0xFFu;
+    if (CLS == SK_I16) return (w[j / 2] >> (16 * (j % 2))) & 0xFFFFu;
+    if (CLS == SK_I32) return w[j];
+    return ((u64)w[2 * j + 1] << 32) | w[2 * j];
+}
+// The column read once.  Without perm_in and with a 16-byte aligned column (vec) a lane takes whole 16-byte accesses: 16, 8, 4 or 2 cells in, as
+// many records out in 16-byte stores; the cells after the last whole run, and every cell read through perm_in, go one by one.
+template <int CLS>
+__global__ __launch_bounds__(RFX_BLOCK) void k_sort_keys32(const void *__restrict__ col, const i64 *__restrict__ perm_in, i64 n, int desc, int vec,
+                                                           u64 *__restrict__ recs, unsigned long long *__restrict__ hist) {
+    constexpr int NDIG = sort_key32_bytes(CLS), R = 16 / sort_src32_bytes(CLS);
+    __shared__ unsigned int lh[NDIG * 256];
+    for (int i = threadIdx.x; i < NDIG * 256; i += RFX_BLOCK) lh[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const i64 tid = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x, nt = (i64)gridDim.x * RFX_BLOCK, nr = (vec && !perm_in) ? n / R : 0;
+    for (i64 g = tid; g < nr; g += nt) {
+        const v4u t = __builtin_nontemporal_load((const v4u *)col + g);
+        const unsigned int w[4] = {t.x, t.y, t.z, t.w};
+        v4u *out = (v4u *)recs + g * (R / 2);
+#pragma unroll
+        for (int j = 0; j < R; j += 2) {
+            const unsigned int k0 = sort_key32(sort_pick32<CLS>(w, j), CLS, desc), k1 = sort_key32(sort_pick32<CLS>(w, j + 1), CLS, desc);
+            sort_hist32<NDIG>(lh, k0, lane);
+            sort_hist32<NDIG>(lh, k1, lane);
+            v4u o;
+            o.x = (unsigned int)(g * R + j); o.y = k0; o.z = (unsigned int)(g * R + j + 1); o.w = k1; // (little-endian: row below key)
+            out[j / 2] = o;
+        }
+    }
+    for (i64 i = nr * R + tid; i < n; i += nt) {
+        u64 x;
+        if (perm_in) {
+            const i64 r = perm_in[i];
+            x = ((u64)r < (u64)n) ? sort_ld32<CLS>(col, r) : (CLS == SK_I32W ? (u64)RFX_NULL_I64_D : 0ULL); // (never a read beyond the column)
+        } else x = sort_ld32<CLS>(col, i);
+        const unsigned int k = sort_key32(x, CLS, desc);
+        recs[i] = ((u64)k << 32) | (u64)(unsigned int)i;
+        sort_hist32<NDIG>(lh, k, lane);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < NDIG * 256; i += RFX_BLOCK)
         if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 
@@ -120,14 +192,15 @@ struct SortPass {
     unsigned int *rows_out;
     i64 *perm_out;               // last pass: the i64 permutation (NULL: not wanted) ...
     const i64 *perm_in;          // ... read through the caller's incoming permutation when given
-    u64 *vals_out;               // last pass: the sorted cells (NULL: not wanted)
+    u64 *vals_out;               // last pass: the sorted cells (NULL: not wanted); packed records: cells of the column's own width
     const u64 *col;              // the column (a NaN's own bits)
     const unsigned int *offsets; // [256][tiles]
     i64 n, tiles;
-    int shift, f64, desc, _pad;
+    int shift, f64, desc, cls; // shift: of the digit inside keys_in's u64 (packed: 32 + 8 d); cls: the packed key's source class (SK_*)
 };
 
-template <int ITEMS>
+// PACKED: keys_in / keys_out hold key << 32 | row records (rows_in / rows_out unused)
+template <int ITEMS, int PACKED>
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(const SortPass P) {
     __shared__ unsigned int cnt[SORT_WAVES][256]; // phase 1: the wave's running digit counts; phase 2: where the wave's first row of a digit goes
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -177,6 +250,18 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(const SortPass P)
         const u64 k = key[s];
         const i64 pos = (i64)(cnt[w][(int)((k >> P.shift) & 255)] + rank[s]);
         if (pos >= P.n) continue; // (cannot happen with consistent counts; never a write beyond the buffers)
+        if (PACKED) {
+            const unsigned int r = (unsigned int)k;
+            if (P.keys_out) P.keys_out[pos] = k;
+            if (P.perm_out) P.perm_out[pos] = P.perm_in ? P.perm_in[r] : (i64)r;
+            if (P.vals_out) {
+                const unsigned int x = sort_cell32((unsigned int)(k >> 32), P.cls, P.desc);
+                if (P.cls == SK_U8) ((unsigned char *)P.vals_out)[pos] = (unsigned char)x;
+                else if (P.cls == SK_I16) ((unsigned short *)P.vals_out)[pos] = (unsigned short)x;
+                else ((unsigned int *)P.vals_out)[pos] = x;
+            }
+            continue;
+        }
         const unsigned int r = P.rows_in ? P.rows_in[i] : (unsigned int)i;
         if (P.keys_out) {
             P.keys_out[pos] = k;
@@ -203,6 +288,21 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_sort_identity(const u64 *__restri
     }
 }
 
+// the same for a key of at most 32 bits: the cells leave in the column's own width (the widened image narrowed)
+template <int CLS>
+__global__ __launch_bounds__(RFX_BLOCK) void k_sort_identity32(const void *__restrict__ col, const i64 *__restrict__ perm_in, i64 n, i64 *__restrict__ perm_out,
+                                                               void *__restrict__ vals_out) {
+    for (i64 i = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * RFX_BLOCK) {
+        if (perm_out) perm_out[i] = perm_in ? perm_in[i] : i;
+        if (vals_out) {
+            const unsigned int x = sort_cell32(sort_key32(sort_ld32<CLS>(col, i), CLS, 0), CLS, 0);
+            if (CLS == SK_U8) ((unsigned char *)vals_out)[i] = (unsigned char)x;
+            else if (CLS == SK_I16) ((unsigned short *)vals_out)[i] = (unsigned short)x;
+            else ((unsigned int *)vals_out)[i] = x;
+        }
+    }
+}
+
 __global__ __launch_bounds__(RFX_BLOCK) void k_inverse_perm(const i64 *__restrict__ perm, i64 n, i64 *__restrict__ out) {
     for (i64 i = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * RFX_BLOCK) {
         const i64 p = perm[i];
@@ -215,14 +315,123 @@ static int sort_grid(const rfx_ctx *c, i64 n) {
     return (int)(want < 1 ? 1 : (want < cap ? want : cap));
 }
 
+// one digit pass of either record form: the tile counts, their scan from the digit's histogram, the scatter
+template <int PACKED>
+static void sort_launch_pass(rfx_ctx *c, int items, const SortPass &P, unsigned int *counts, const unsigned long long *digit_hist) {
+    const dim3 grid((unsigned)P.tiles), block(SORT_THREADS);
+    if (items == SORT_ITEMS) hipLaunchKernelGGL((k_sort_count<SORT_ITEMS>), grid, block, 0, c->stream, P.keys_in, P.n, P.shift, P.tiles, counts);
+    else hipLaunchKernelGGL((k_sort_count<SORT_SMALL_ITEMS>), grid, block, 0, c->stream, P.keys_in, P.n, P.shift, P.tiles, counts);
+    hipLaunchKernelGGL(k_sort_scan, dim3(256), dim3(RFX_BLOCK), 0, c->stream, counts, P.tiles, digit_hist);
+    if (items == SORT_ITEMS) hipLaunchKernelGGL((k_sort_scatter<SORT_ITEMS, PACKED>), grid, block, 0, c->stream, P);
+    else hipLaunchKernelGGL((k_sort_scatter<SORT_SMALL_ITEMS, PACKED>), grid, block, 0, c->stream, P);
+}
+// the source class of a key of at most 32 bits (-1: another type)
+static int sort_class32(int32_t type) {
+    switch (type) {
+        case RFX_B8: case RFX_U8: return SK_U8;
+        case RFX_I16: return SK_I16;
+        case RFX_I32: return SK_I32;
+        case RFX_I32_WIDE: return SK_I32W;
+        default: return -1;
+    }
+}
+template <int CLS>
+static void sort_launch_keys32(rfx_ctx *c, const void *d_col, const i64 *d_perm_in, i64 n, int desc, u64 *recs, unsigned long long *hist) {
+    const int vec = ((uintptr_t)d_col & 15) == 0;
+    const i64 per = (vec && !d_perm_in) ? 16 / sort_src32_bytes(CLS) : 1;
+    hipLaunchKernelGGL((k_sort_keys32<CLS>), dim3(sort_grid(c, (n + per - 1) / per)), dim3(RFX_BLOCK), 0, c->stream, d_col, d_perm_in, n, desc, vec, recs, hist);
+}
+template <int CLS>
+static void sort_launch_identity32(rfx_ctx *c, const void *d_col, const i64 *d_perm_in, i64 n, i64 *d_perm_out, void *d_vals_out) {
+    hipLaunchKernelGGL((k_sort_identity32<CLS>), dim3(sort_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, d_col, d_perm_in, n, d_perm_out, d_vals_out);
+}
+#define SORT_BY_CLASS32(cls, fn, ...)                         \
+    do {                                                      \
+        if ((cls) == SK_U8) fn<SK_U8>(__VA_ARGS__);           \
+        else if ((cls) == SK_I16) fn<SK_I16>(__VA_ARGS__);    \
+        else if ((cls) == SK_I32) fn<SK_I32>(__VA_ARGS__);    \
+        else fn<SK_I32W>(__VA_ARGS__);                        \
+    } while (0)
+
+// keys of at most 32 bits: one pair of n packed records, the histograms and passes the key's width has
+static int sort_run32(rfx_ctx *c, const void *d_col, int cls, i64 n, int desc, const i64 *d_perm_in, i64 *d_perm_out, void *d_vals_out, int32_t *passes) {
+    const int ndig = sort_key32_bytes(cls);
+    const int items = n < SORT_SMALL_ROWS ? SORT_SMALL_ITEMS : SORT_ITEMS;
+    const i64 tile = (i64)SORT_THREADS * items, tiles = (n + tile - 1) / tile;
+    // scratch: records A | records B | counts [256][tiles] | histograms [ndig][256]   (every part 16-byte aligned)
+    const size_t kb = (((size_t)n * 8) + 15) & ~(size_t)15, cb = (size_t)tiles * 256 * 4, hb = (size_t)ndig * 256 * 8;
+    void *scratch = NULL;
+    int rc = rfx_hip_malloc((rfx_ctx_t *)c, &scratch, 2 * kb + cb + hb);
+    if (rc != RFX_OK) return rc;
+    char *sp = (char *)scratch;
+    u64 *recs[2] = {(u64 *)sp, (u64 *)(sp + kb)};
+    unsigned int *counts = (unsigned int *)(sp + 2 * kb);
+    unsigned long long *hist = (unsigned long long *)(sp + 2 * kb + cb);
+    unsigned long long h[4 * 256];
+    hipError_t e = hipMemsetAsync(hist, 0, hb, c->stream);
+    RFX_KERNEL_BEGIN(c);
+    if (e == hipSuccess) {
+        SORT_BY_CLASS32(cls, sort_launch_keys32, c, d_col, d_perm_in, n, desc, recs[0], hist);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, hist, hb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    int todo[4], ntodo = 0;
+    if (e == hipSuccess) {
+        for (int d = 0; d < ndig; d++) {
+            int one = 0;
+            for (int b = 0; b < 256 && !one; b++) one = h[d * 256 + b] == (unsigned long long)n;
+            if (!one) todo[ntodo++] = d;
+        }
+    }
+    int cur = 0;
+    for (int p = 0; p < ntodo && e == hipSuccess; p++) {
+        const int last = p == ntodo - 1;
+        SortPass P;
+        memset(&P, 0, sizeof(P));
+        P.keys_in = recs[cur];
+        if (!last) P.keys_out = recs[cur ^ 1];
+        else {
+            P.perm_out = d_perm_out;
+            P.perm_in = d_perm_in;
+            P.vals_out = (u64 *)d_vals_out;
+        }
+        P.offsets = counts;
+        P.n = n;
+        P.tiles = tiles;
+        P.shift = 32 + 8 * todo[p];
+        P.desc = desc;
+        P.cls = cls;
+        sort_launch_pass<1>(c, items, P, counts, hist + 256 * todo[p]);
+        e = hipGetLastError();
+        cur ^= 1;
+    }
+    if (e == hipSuccess && ntodo == 0) {
+        SORT_BY_CLASS32(cls, sort_launch_identity32, c, d_col, d_perm_in, n, d_perm_out, d_vals_out);
+        e = hipGetLastError();
+    }
+    RFX_KERNEL_END(c);
+    const hipError_t es = hipStreamSynchronize(c->stream); // (the scratch goes back to the context's pool: nothing may still read it)
+    rfx_hip_free((rfx_ctx_t *)c, scratch);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        rfx_set_error("rfx_sort: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? RFX_ENOMEM : RFX_EHIP;
+    }
+    if (passes) *passes = ntodo;
+    return RFX_OK;
+}
+
 static int sort_run(rfx_ctx *c, const void *d_col, int32_t type, i64 n, int desc, const i64 *d_perm_in, i64 *d_perm_out, u64 *d_vals_out, int32_t *passes) {
     RFX_REQUIRE(c, RFX_EINVAL, "NULL context");
-    RFX_REQUIRE(type == RFX_I64 || type == RFX_F64, RFX_EINVAL, "key type must be i64 (timestamp) or f64");
+    const int cls32 = sort_class32(type);
+    RFX_REQUIRE(type == RFX_I64 || type == RFX_F64 || cls32 >= 0, RFX_EINVAL, "key type must be i64 (timestamp), f64, i32 (date, time; raw or widened), i16, u8 or b8");
     RFX_REQUIRE(n >= 0, RFX_EINVAL, "negative size");
     RFX_REQUIRE(n == 0 || (d_col && (d_perm_out || d_vals_out)), RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(n <= SORT_MAX_ROWS, RFX_ELIMIT, "more than 2^32 - 1 rows (rows travel as 4 bytes)");
     if (passes) *passes = 0;
     if (n == 0) return RFX_OK;
+    if (cls32 >= 0) return sort_run32(c, d_col, cls32, n, desc, d_perm_in, d_perm_out, d_vals_out, passes);
     const int f64 = type == RFX_F64;
     const int items = n < SORT_SMALL_ROWS ? SORT_SMALL_ITEMS : SORT_ITEMS;
     const i64 tile = (i64)SORT_THREADS * items, tiles = (n + tile - 1) / tile;
@@ -275,15 +484,7 @@ static int sort_run(rfx_ctx *c, const void *d_col, int32_t type, i64 n, int desc
         P.shift = 8 * todo[p];
         P.f64 = f64;
         P.desc = desc;
-        if (items == SORT_ITEMS) {
-            hipLaunchKernelGGL((k_sort_count<SORT_ITEMS>), dim3((unsigned)tiles), dim3(SORT_THREADS), 0, c->stream, (const u64 *)keys[cur], n, P.shift, tiles, counts);
-            hipLaunchKernelGGL(k_sort_scan, dim3(256), dim3(RFX_BLOCK), 0, c->stream, counts, tiles, (const unsigned long long *)(hist + 256 * todo[p]));
-            hipLaunchKernelGGL((k_sort_scatter<SORT_ITEMS>), dim3((unsigned)tiles), dim3(SORT_THREADS), 0, c->stream, P);
-        } else {
-            hipLaunchKernelGGL((k_sort_count<SORT_SMALL_ITEMS>), dim3((unsigned)tiles), dim3(SORT_THREADS), 0, c->stream, (const u64 *)keys[cur], n, P.shift, tiles, counts);
-            hipLaunchKernelGGL(k_sort_scan, dim3(256), dim3(RFX_BLOCK), 0, c->stream, counts, tiles, (const unsigned long long *)(hist + 256 * todo[p]));
-            hipLaunchKernelGGL((k_sort_scatter<SORT_SMALL_ITEMS>), dim3((unsigned)tiles), dim3(SORT_THREADS), 0, c->stream, P);
-        }
+        sort_launch_pass<0>(c, items, P, counts, hist + 256 * todo[p]);
         e = hipGetLastError();
         cur ^= 1;
         have_rows = 1;

@@ -23,6 +23,18 @@ from ._lib import RfxError
 from .marshal import NotFused as _NotFused, ctype_of as _ctype_of
 
 Column = torch.Tensor
+_NARROW_SORT_TYPES = {torch.int32: L.RFX_I32, torch.int16: L.RFX_I16, torch.uint8: L.RFX_U8, torch.bool: L.RFX_B8}
+
+
+def _sort_type_of(t: torch.Tensor) -> int:
+    """A sort key column's type code: the 8-byte ones, or a narrow one as its raw cells."""
+    narrow = _NARROW_SORT_TYPES.get(t.dtype)
+    return narrow if narrow is not None else _ctype_of(t)
+
+
+def _no_narrow_over_shards(cols) -> None:
+    if any(c.dtype in _NARROW_SORT_TYPES for c in cols):
+        raise RfxError("sort: 1-, 2- and 4-byte key columns do not sort over shards (rfx_exec_sort_shards takes i64 / f64 pieces)")
 
 
 class _Owner:
@@ -353,19 +365,22 @@ class Engine:
         return out
 
     def sort_index(self, columns, descending: bool = False, over_shards: bool = False) -> torch.Tensor:
-        """The stable order of the rows by ``columns`` (one i64 / f64 device column or a sequence, the first most significant; all
-        ascending or all descending) as an i64 device column: iasc / idesc, and the permutation behind xasc / xdesc (rfx_exec_sort).
+        """The stable order of the rows by ``columns`` (one device column or a sequence, the first most significant; all ascending or all
+        descending) as an i64 device column: iasc / idesc, and the permutation behind xasc / xdesc (rfx_exec_sort).  Columns are int64 /
+        float64, or the narrow key types int32 (INT32_MIN is the null: first ascending), int16, uint8 and bool (ordered as bytes), which sort
+        as packed 8-byte records; a sequence may mix them.
         ``over_shards`` on an engine of several shards: every shard sorts its rows, one stable multiway merge (rfx_exec_sort_shards) -- the
-        same answer bit for bit; without it a sharded engine refuses ("sort over a sharded table")."""
+        same answer bit for bit, int64 / float64 columns only; without it a sharded engine refuses ("sort over a sharded table")."""
         cols = [columns] if isinstance(columns, torch.Tensor) else list(columns)
         if not cols:
             raise RfxError("sort_index needs at least one column")
         n = cols[0].numel()
         for c in cols:
             self._check_col(c, n)
-        types = (C.c_int32 * len(cols))(*[_ctype_of(c) for c in cols])
+        types = (C.c_int32 * len(cols))(*[_sort_type_of(c) for c in cols])
         out = torch.empty(n, dtype=torch.int64, device=self.device)
         if over_shards and self.shards > 1:
+            _no_narrow_over_shards(cols)
             self._sort_shards(cols, types, descending, n, out.data_ptr(), None)
             return out
         ptrs = (C.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
@@ -373,13 +388,15 @@ class Engine:
         return out
 
     def sort_values(self, col: torch.Tensor, descending: bool = False, over_shards: bool = False) -> torch.Tensor:
-        """asc / desc: the column's own cells in sorted order (rfx_exec_sort_values; ``over_shards`` as for sort_index)."""
+        """asc / desc: the column's own cells in sorted order, in the column's dtype (rfx_exec_sort_values; column types and ``over_shards``
+        as for sort_index)."""
         self._check_col(col)
         out = torch.empty_like(col)
         if over_shards and self.shards > 1:
+            _no_narrow_over_shards([col])
             self._sort_shards([col], (C.c_int32 * 1)(_ctype_of(col)), descending, col.numel(), None, out.data_ptr())
             return out
-        self._xcheck(self.lib.rfx_exec_sort_values(self._x, col.data_ptr(), _ctype_of(col), int(bool(descending)), col.numel(), out.data_ptr(), None), "sort")
+        self._xcheck(self.lib.rfx_exec_sort_values(self._x, col.data_ptr(), _sort_type_of(col), int(bool(descending)), col.numel(), out.data_ptr(), None), "sort")
         return out
 
     def _sort_shards(self, cols, types, descending, n, d_perm, d_values):

@@ -11,8 +11,16 @@ counters) and the total, and the merge's bytes -- (8 * keys + 8) read and 8 writ
 runs the merge with another splitter tile (RFX_MERGE_TILE; 0 = the shipped one).  Beside the four cases, per shard count one whose runs interleave
 record by record (row mod the shard span): every gap between splitters then holds a tile of every run -- the merge's worst case.
 
+--narrow: instead, the packed-record path over keys of at most 32 bits: iasc of uniform full-range I32 keys (negatives included), of I32 keys in
+[0, 1e6), of DATE keys with 10 % nulls, of I16 and of U8 keys.  Per arm, in one process and alternating step by step: the packed path over the raw
+cells, for the I32 arms the 8-byte path over the same cells' widened image (rfx_hip_widen_i32 -- what the operator layer could have run with no new
+kernel), and torch.sort(stable=True) of the same tensor.  Per path the median, the fastest and the slowest step, the passes, and the bytes of the
+passes' traffic model (8 B count + 16 B scatter per row and pass for packed records; 8 + 24 for the 8-byte path) over the median against 8 TB/s.
+--out FILE appends the JSON lines to FILE as well.
+
     python tools/bench_sort.py [--rows 100000000,1000000000] [--ref-rows 100000000] [--steps 5] [--warmup 1]
     python tools/bench_sort.py --rows 100000000 --shards 2,4,8 [--tile 2048]
+    python tools/bench_sort.py --narrow --rows 100000000 --steps 7 --warmup 2 [--out profiles/sort_narrow_bench_run1.jsonl]
 """
 import argparse
 import ctypes as C
@@ -99,6 +107,72 @@ def sharded(a):
     eng.close()
 
 
+def narrow_arms(a):
+    eng = Engine(0)
+    g = torch.Generator(device=eng.device).manual_seed(1)
+    i32min = -(1 << 31)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def passes_of(fn):
+        before = eng.xstat(L.RFX_XSTAT_SORT_PASSES)
+        fn()
+        return eng.xstat(L.RFX_XSTAT_SORT_PASSES) - before
+
+    for n in [int(x) for x in a.rows.split(",")]:
+        arms = [("iasc i32 full range", lambda: torch.randint(i32min, 1 << 31, (n,), dtype=torch.int64, device=eng.device, generator=g).to(torch.int32), True),
+                ("iasc i32 [0,1e6)", lambda: torch.randint(0, 1_000_000, (n,), dtype=torch.int32, device=eng.device, generator=g), True),
+                ("iasc date, 10% nulls", lambda: torch.where(torch.rand(n, device=eng.device, generator=g) < 0.1, i32min,
+                                                              torch.randint(0, 20_000, (n,), dtype=torch.int32, device=eng.device, generator=g)).to(torch.int32), True),
+                ("iasc i16 full range", lambda: torch.randint(-(1 << 15), 1 << 15, (n,), dtype=torch.int16, device=eng.device, generator=g), False),
+                ("iasc u8 full range", lambda: torch.randint(0, 256, (n,), dtype=torch.uint8, device=eng.device, generator=g), False)]
+        for case, make, is_i32 in arms:
+            col = make()
+            paths = {"packed": lambda: eng.sort_index(col)}
+            if is_i32:
+                wide = torch.empty(n, dtype=torch.int64, device=eng.device)
+                L.check(eng.lib.rfx_hip_widen_i32(eng._ctx, col.data_ptr(), n, wide.data_ptr()), "widen_i32")
+                eng.sync()
+                paths["wide8"] = lambda: eng.sort_index(wide)
+            if not a.no_torch:
+                paths["torch"] = lambda: torch.sort(col, stable=True)
+            passes = {k: passes_of(f) for k, f in paths.items() if k != "torch"}
+            for _ in range(a.warmup):
+                for f in paths.values():
+                    f()
+            ts = {k: [] for k in paths}
+            for _ in range(a.steps):  # alternating: every step times every path once
+                for k, f in paths.items():
+                    ts[k].append(once(f))
+            row = {"case": case, "rows": n, "steps": a.steps, "warmup": a.warmup}
+            for k, v in ts.items():
+                v.sort()
+                row[k + "_ms"], row[k + "_ms_min"], row[k + "_ms_max"] = round(v[len(v) // 2], 3), round(v[0], 3), round(v[-1], 3)
+            for k, per_pass in (("packed", 24), ("wide8", 32)):
+                if k in passes:
+                    moved = n * per_pass * passes[k]
+                    row[k + "_passes"], row[k + "_model_gb"] = passes[k], round(moved / 1e9, 2)
+                    row[k + "_model_of_8tb_s"] = round(moved / row[k + "_ms"] / 1e9 / 8.0, 3)
+            if "wide8" in ts:
+                row["packed_over_wide8"] = round(row["packed_ms"] / row["wide8_ms"], 3)
+            line = json.dumps(row)
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+            del col, paths
+            if is_i32:
+                del wide
+            torch.cuda.empty_cache()
+            eng.trim()
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="100000000,1000000000")
@@ -108,7 +182,11 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--shards", default="")
     ap.add_argument("--tile", type=int, default=0)
+    ap.add_argument("--narrow", action="store_true")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.narrow:
+        return narrow_arms(a)
     if a.shards:
         return sharded(a)
     eng = Engine(0)
