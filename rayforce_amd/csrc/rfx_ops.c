@@ -34,6 +34,89 @@ obj_p rfx_host_err(const char *msg);
 obj_p rfx_host_eval(obj_p o);
 void rfx_host_trim(void);
 
+/* ------------------------------------------------------------------------------------------------ the verb table */
+/* ONE row per built-in: V(id, the host's symbol, our entry point or NULL, the name the standalone host binds it to or NULL, the function object's type,
+ * its attribute).  The F_* ids, the host's functions (H.f, bound by symbol), our entry points (fn_id recognises both inside parsed expressions) and
+ * rfx_host_fn's lookup are all generated from it: a new verb is one new row and its implementation.  Row order is id order.
+ * Three runs are addressed by range or by offset and must stay as they are (the _Static_asserts below):
+ *   F_SUM .. F_FIRST  the aggregates rfx_select and rfx_update map: they test that id RANGE (rfx_select also takes, by name, F_LAST, F_MED and F_DEV);
+ *   F_EQ .. F_GE      cmp_impl calls the host's H.f[F_EQ + op], op = RFX_EQ .. RFX_GE;
+ *   F_ADD .. F_MOD    build_xnodes maps an operator to RFX_X_ADD + (f - F_ADD).
+ * The ids after F_BINR lie outside the aggregates' range: window_agg (rfx_ops_window.c) recognises F_LAST and refuses F_DEV; F_DISTINCT .. F_UNION (and
+ * F_IN as a verb of its own) are the set verbs of rfx_ops_set.c, which no reader of fn_id maps -- inside where: F_IN stays the comparison list of
+ * rfx_ops_plan.c and nothing else.  `not` is recognised inside where: only; xbar inside `by:` is recognised by its function object and
+ * bucketed by the planner, called as a verb it is rfx_xbar.  "div" is the reference's ray_fdiv (our rfx_div), "/" its ray_div (our rfx_floordiv).
+ * rfx_select's take: stays the host's H.f[F_TAKE]. */
+#define RFX_VERBS(V)                                                                                  \
+    /* F_SUM .. F_FIRST: one run, addressed as a range */                                             \
+    V(F_SUM, "ray_sum", rfx_sum, "sum", RFX_TYPE_UNARY, RFX_FN_AGGR)                                  \
+    V(F_AVG, "ray_avg", rfx_avg, "avg", RFX_TYPE_UNARY, RFX_FN_AGGR)                                  \
+    V(F_MIN, "ray_min", rfx_min, "min", RFX_TYPE_UNARY, RFX_FN_AGGR)                                  \
+    V(F_MAX, "ray_max", rfx_max, "max", RFX_TYPE_UNARY, RFX_FN_AGGR)                                  \
+    V(F_COUNT, "ray_count", rfx_count, "count", RFX_TYPE_UNARY, RFX_FN_AGGR)                          \
+    V(F_FIRST, "ray_first", rfx_first, "first", RFX_TYPE_UNARY, RFX_FN_AGGR)                          \
+    /* F_EQ .. F_GE: one run, addressed as F_EQ + RFX_EQ .. RFX_GE */                                 \
+    V(F_EQ, "ray_eq", rfx_eq, "==", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                   \
+    V(F_NE, "ray_ne", rfx_ne, "!=", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                   \
+    V(F_LT, "ray_lt", rfx_lt, "<", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                    \
+    V(F_GT, "ray_gt", rfx_gt, ">", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                    \
+    V(F_LE, "ray_le", rfx_le, "<=", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                   \
+    V(F_GE, "ray_ge", rfx_ge, ">=", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                   \
+    V(F_AND, "ray_and", rfx_and, "and", RFX_TYPE_VARY, RFX_FN_SPECIAL_FORM)                           \
+    V(F_OR, "ray_or", rfx_or, "or", RFX_TYPE_VARY, RFX_FN_SPECIAL_FORM)                               \
+    V(F_SELECT, "ray_select", rfx_select, "select", RFX_TYPE_UNARY, RFX_FN_NONE)                      \
+    /* F_ADD .. F_MOD: one run, addressed as RFX_X_ADD + (f - F_ADD) */                               \
+    V(F_ADD, "ray_add", rfx_add, "+", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                 \
+    V(F_SUB, "ray_sub", rfx_sub, "-", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                 \
+    V(F_MUL, "ray_mul", rfx_mul, "*", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                 \
+    V(F_FDIV, "ray_fdiv", rfx_div, "div", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                             \
+    V(F_DIV, "ray_div", rfx_floordiv, "/", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                            \
+    V(F_MOD, "ray_mod", rfx_mod, "%", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                                 \
+    V(F_XBAR, "ray_xbar", rfx_xbar, "xbar", RFX_TYPE_BINARY, RFX_FN_ATOMIC)                           \
+    V(F_LJ, "ray_left_join", rfx_left_join, NULL, RFX_TYPE_VARY, RFX_FN_NONE)                         \
+    V(F_IJ, "ray_inner_join", rfx_inner_join, NULL, RFX_TYPE_VARY, RFX_FN_NONE)                       \
+    V(F_UPDATE, "ray_update", rfx_update, "update", RFX_TYPE_UNARY, RFX_FN_NONE)                      \
+    V(F_TAKE, "ray_take", rfx_take, "take", RFX_TYPE_BINARY, RFX_FN_NONE)                             \
+    V(F_IN, "ray_in", rfx_in, "in", RFX_TYPE_BINARY, RFX_FN_NONE)                                     \
+    V(F_WITHIN, "ray_within", rfx_within, NULL, RFX_TYPE_BINARY, RFX_FN_NONE)                         \
+    V(F_NOT, "ray_not", NULL, NULL, RFX_TYPE_UNARY, RFX_FN_NONE)                                      \
+    V(F_MED, "ray_med", rfx_med, "med", RFX_TYPE_UNARY, RFX_FN_AGGR)                                  \
+    V(F_IASC, "ray_iasc", rfx_iasc, "iasc", RFX_TYPE_UNARY, RFX_FN_NONE)                              \
+    V(F_IDESC, "ray_idesc", rfx_idesc, "idesc", RFX_TYPE_UNARY, RFX_FN_NONE)                          \
+    V(F_ASC, "ray_asc", rfx_asc, "asc", RFX_TYPE_UNARY, RFX_FN_NONE)                                  \
+    V(F_DESC, "ray_desc", rfx_desc, "desc", RFX_TYPE_UNARY, RFX_FN_NONE)                              \
+    V(F_RANK, "ray_rank", rfx_rank, "rank", RFX_TYPE_UNARY, RFX_FN_NONE)                              \
+    V(F_XASC, "ray_xasc", rfx_xasc, "xasc", RFX_TYPE_BINARY, RFX_FN_NONE)                             \
+    V(F_XDESC, "ray_xdesc", rfx_xdesc, "xdesc", RFX_TYPE_BINARY, RFX_FN_NONE)                         \
+    V(F_AJ, "ray_asof_join", rfx_asof_join, "asof-join", RFX_TYPE_VARY, RFX_FN_NONE)                  \
+    V(F_BIN, "ray_bin", rfx_bin, "bin", RFX_TYPE_BINARY, RFX_FN_NONE)                                 \
+    V(F_BINR, "ray_binr", rfx_binr, "binr", RFX_TYPE_BINARY, RFX_FN_NONE)                             \
+    V(F_WJ, "ray_window_join", rfx_window_join, "window-join", RFX_TYPE_VARY, RFX_FN_NONE)            \
+    V(F_WJ1, "ray_window_join1", rfx_window_join1, "window-join1", RFX_TYPE_VARY, RFX_FN_NONE)        \
+    V(F_LAST, "ray_last", rfx_last, "last", RFX_TYPE_UNARY, RFX_FN_AGGR)                              \
+    V(F_DISTINCT, "ray_distinct", rfx_distinct, "distinct", RFX_TYPE_UNARY, RFX_FN_NONE)              \
+    V(F_FIND, "ray_find", rfx_find, "find", RFX_TYPE_BINARY, RFX_FN_NONE)                             \
+    V(F_SECT, "ray_sect", rfx_sect, "sect", RFX_TYPE_BINARY, RFX_FN_NONE)                             \
+    V(F_EXCEPT, "ray_except", rfx_except, "except", RFX_TYPE_BINARY, RFX_FN_NONE)                     \
+    V(F_UNION, "ray_union", rfx_union, "union", RFX_TYPE_BINARY, RFX_FN_NONE)                         \
+    V(F_DEV, "ray_dev", rfx_dev, "dev", RFX_TYPE_UNARY, RFX_FN_AGGR)                                  \
+    V(F_XRANK, "ray_xrank", rfx_xrank, "xrank", RFX_TYPE_BINARY, RFX_FN_NONE)                         \
+    V(F_FLOOR, "ray_floor", rfx_floor, "floor", RFX_TYPE_UNARY, RFX_FN_ATOMIC)                        \
+    V(F_CEIL, "ray_ceil", rfx_ceil, "ceil", RFX_TYPE_UNARY, RFX_FN_ATOMIC)                            \
+    V(F_ROUND, "ray_round", rfx_round, "round", RFX_TYPE_UNARY, RFX_FN_ATOMIC)                        \
+    V(F_NEG, "ray_neg", rfx_neg, "neg", RFX_TYPE_UNARY, RFX_FN_ATOMIC)                                \
+    V(F_FILTER, "ray_filter", rfx_filter, "filter", RFX_TYPE_BINARY, RFX_FN_NONE)                     \
+    V(F_REVERSE, "ray_reverse", rfx_reverse, "reverse", RFX_TYPE_UNARY, RFX_FN_NONE)                  \
+    V(F_AS, "ray_cast_obj", rfx_as, "as", RFX_TYPE_BINARY, RFX_FN_NONE)
+#define V(id, host, ours, name, type, attrs) id,
+enum { RFX_VERBS(V) F_N };
+#undef V
+#define V(id, host, ours, name, type, attrs) [id] = {host, (void *)(ours), name, type, attrs},
+static const struct { const char *host; void *ours; const char *name; int type, attrs; } VERB[F_N] = {RFX_VERBS(V)};
+#undef V
+_Static_assert(F_SUM == 0 && F_AVG == F_SUM + 1 && F_MIN == F_SUM + 2 && F_MAX == F_SUM + 3 && F_COUNT == F_SUM + 4 && F_FIRST == F_SUM + 5, "F_SUM .. F_FIRST: the aggregates' id range");
+_Static_assert(F_NE == F_EQ + RFX_NE && F_LT == F_EQ + RFX_LT && F_GT == F_EQ + RFX_GT && F_LE == F_EQ + RFX_LE && F_GE == F_EQ + RFX_GE && RFX_EQ == 0, "F_EQ .. F_GE follow RFX_EQ .. RFX_GE");
+_Static_assert(F_SUB - F_ADD == RFX_X_SUB - RFX_X_ADD && F_MUL - F_ADD == RFX_X_MUL - RFX_X_ADD && F_FDIV - F_ADD == RFX_X_FDIV - RFX_X_ADD && F_DIV - F_ADD == RFX_X_DIV - RFX_X_ADD && F_MOD - F_ADD == RFX_X_MOD - RFX_X_ADD, "F_ADD .. F_MOD follow RFX_X_ADD .. RFX_X_MOD");
 /* ------------------------------------------------------------------------------------------------ host binding */
 static struct {
     int bound; /* 0 = not yet, 1 = reference host, 2 = standalone */
@@ -48,24 +131,9 @@ static struct {
     int64_t (*intern)(const char *, int64_t);
     const char *(*symname)(int64_t);
     obj_p null_obj;
-    /* the host's own built-ins, for recognising function objects inside parsed expressions and for delegation */
-    void *f[64];
+    /* the host's own built-ins by verb id (all NULL without a host), for recognising function objects inside parsed expressions and for delegation */
+    void *f[F_N];
 } H;
-/* F_SUM .. F_FIRST are the aggregates rfx_update maps: it tests that id RANGE.  rfx_select maps the same range and, by name, F_LAST, F_MED and F_DEV.
- * The ids after F_BINR lie outside the range: window_agg (rfx_ops_window.c) recognises F_LAST and refuses F_DEV; F_DISTINCT .. F_UNION (and F_IN as a
- * verb of its own) are the set verbs of rfx_ops_set.c, which no reader of fn_id maps -- inside where: F_IN stays the comparison list of
- * rfx_ops_plan.c and nothing else. */
-enum { F_SUM, F_AVG, F_MIN, F_MAX, F_COUNT, F_FIRST, F_EQ, F_NE, F_LT, F_GT, F_LE, F_GE, F_AND, F_OR, F_SELECT, F_ADD, F_SUB, F_MUL, F_FDIV, F_DIV, F_MOD, F_XBAR, F_LJ, F_IJ, F_UPDATE, F_TAKE, F_IN, F_WITHIN, F_NOT, F_MED, F_IASC, F_IDESC, F_ASC, F_DESC, F_RANK, F_XASC, F_XDESC, F_AJ, F_BIN, F_BINR, F_WJ, F_WJ1, F_LAST, F_DISTINCT, F_FIND, F_SECT, F_EXCEPT, F_UNION, F_DEV, F_XRANK, F_FLOOR, F_CEIL, F_ROUND, F_NEG, F_FILTER, F_REVERSE, F_AS, F_N };
-static const char *HOST_FN[F_N] = {"ray_sum", "ray_avg", "ray_min", "ray_max", "ray_count", "ray_first", "ray_eq",  "ray_ne",  "ray_lt",  "ray_gt",
-                                   "ray_le",  "ray_ge",  "ray_and", "ray_or",  "ray_select", "ray_add",  "ray_sub", "ray_mul", "ray_fdiv", "ray_div", "ray_mod", "ray_xbar",
-                                   "ray_left_join", "ray_inner_join", "ray_update", "ray_take", "ray_in", "ray_within", "ray_not", "ray_med",
-                                   "ray_iasc", "ray_idesc", "ray_asc", "ray_desc", "ray_rank", "ray_xasc", "ray_xdesc",
-                                   "ray_asof_join", "ray_bin", "ray_binr", "ray_window_join", "ray_window_join1", "ray_last",
-                                   "ray_distinct", "ray_find", "ray_sect", "ray_except", "ray_union", "ray_dev",
-                                   "ray_xrank", "ray_floor", "ray_ceil", "ray_round", "ray_neg", "ray_filter", "ray_reverse", "ray_cast_obj"}; /* (not: recognised inside where: only; in / within also verbs of their own) */
-/* xbar inside `by:` is recognised by its function object (fn_id -> F_XBAR) and bucketed by the planner; called as a verb it is rfx_xbar
- * (rfx_ops_bucket.c), which the standalone object model binds to "xbar". */
-static void *OUR_FN[F_N];
 static void *g_host_where, *g_host_at, *g_host_group; /* the host's built-ins behind rfx_where / rfx_at / rfx_group (NULL without a host) */
 static char g_err[640];
 static int g_last_gpu = 0;
@@ -75,22 +143,6 @@ int rfx_last_select_on_gpu(void) { return g_last_gpu; }
 
 int rfx_host_bind(void) {
     if (H.bound) return H.bound == 1;
-    OUR_FN[F_SUM] = (void *)rfx_sum; OUR_FN[F_AVG] = (void *)rfx_avg; OUR_FN[F_MIN] = (void *)rfx_min; OUR_FN[F_MAX] = (void *)rfx_max;
-    OUR_FN[F_COUNT] = (void *)rfx_count; OUR_FN[F_FIRST] = (void *)rfx_first; OUR_FN[F_EQ] = (void *)rfx_eq; OUR_FN[F_NE] = (void *)rfx_ne;
-    OUR_FN[F_LT] = (void *)rfx_lt; OUR_FN[F_GT] = (void *)rfx_gt; OUR_FN[F_LE] = (void *)rfx_le; OUR_FN[F_GE] = (void *)rfx_ge;
-    OUR_FN[F_AND] = (void *)rfx_and; OUR_FN[F_OR] = (void *)rfx_or; OUR_FN[F_SELECT] = (void *)rfx_select;
-    OUR_FN[F_ADD] = (void *)rfx_add; OUR_FN[F_SUB] = (void *)rfx_sub; OUR_FN[F_MUL] = (void *)rfx_mul; OUR_FN[F_FDIV] = (void *)rfx_div; OUR_FN[F_DIV] = (void *)rfx_floordiv; OUR_FN[F_MOD] = (void *)rfx_mod;
-    OUR_FN[F_XBAR] = (void *)rfx_xbar; OUR_FN[F_WITHIN] = (void *)rfx_within; OUR_FN[F_XRANK] = (void *)rfx_xrank;
-    OUR_FN[F_FLOOR] = (void *)rfx_floor; OUR_FN[F_CEIL] = (void *)rfx_ceil; OUR_FN[F_ROUND] = (void *)rfx_round; OUR_FN[F_NEG] = (void *)rfx_neg;
-    OUR_FN[F_LJ] = (void *)rfx_left_join; OUR_FN[F_IJ] = (void *)rfx_inner_join; OUR_FN[F_UPDATE] = (void *)rfx_update;
-    OUR_FN[F_MED] = (void *)rfx_med; /* (not inside the F_SUM..F_FIRST range the select / update mappings check: select takes it by name) */
-    OUR_FN[F_IASC] = (void *)rfx_iasc; OUR_FN[F_IDESC] = (void *)rfx_idesc; OUR_FN[F_ASC] = (void *)rfx_asc; OUR_FN[F_DESC] = (void *)rfx_desc;
-    OUR_FN[F_RANK] = (void *)rfx_rank; OUR_FN[F_XASC] = (void *)rfx_xasc; OUR_FN[F_XDESC] = (void *)rfx_xdesc;
-    OUR_FN[F_AJ] = (void *)rfx_asof_join; OUR_FN[F_BIN] = (void *)rfx_bin; OUR_FN[F_BINR] = (void *)rfx_binr;
-    OUR_FN[F_WJ] = (void *)rfx_window_join; OUR_FN[F_WJ1] = (void *)rfx_window_join1; OUR_FN[F_LAST] = (void *)rfx_last; OUR_FN[F_DEV] = (void *)rfx_dev;
-    OUR_FN[F_IN] = (void *)rfx_in; OUR_FN[F_DISTINCT] = (void *)rfx_distinct; OUR_FN[F_FIND] = (void *)rfx_find; OUR_FN[F_SECT] = (void *)rfx_sect;
-    OUR_FN[F_EXCEPT] = (void *)rfx_except; OUR_FN[F_UNION] = (void *)rfx_union;
-    OUR_FN[F_TAKE] = (void *)rfx_take; OUR_FN[F_FILTER] = (void *)rfx_filter; OUR_FN[F_REVERSE] = (void *)rfx_reverse; OUR_FN[F_AS] = (void *)rfx_as; /* (rfx_select's take: stays the host's: H.f[F_TAKE]) */
     void *v = dlsym(RTLD_DEFAULT, "vector"), *t = dlsym(RTLD_DEFAULT, "table"), *e = dlsym(RTLD_DEFAULT, "eval");
     void *rs = dlsym(RTLD_DEFAULT, "ray_select"), *nu = dlsym(RTLD_DEFAULT, "__NULL_OBJ");
     if (v && t && e && rs && nu && !getenv("RFX_FORCE_STANDALONE")) {
@@ -105,7 +157,7 @@ int rfx_host_bind(void) {
         H.intern = (int64_t(*)(const char *, int64_t))dlsym(RTLD_DEFAULT, "symbols_intern");
         H.symname = (const char *(*)(int64_t))dlsym(RTLD_DEFAULT, "str_from_symbol");
         H.null_obj = (obj_p)nu;
-        for (int i = 0; i < F_N; i++) H.f[i] = dlsym(RTLD_DEFAULT, HOST_FN[i]);
+        for (int i = 0; i < F_N; i++) H.f[i] = dlsym(RTLD_DEFAULT, VERB[i].host);
         g_host_where = dlsym(RTLD_DEFAULT, "ray_where"); /* (not in H.f: never recognised inside a query, only handed back to -- refused1x) */
         g_host_at = dlsym(RTLD_DEFAULT, "ray_at");
         g_host_group = dlsym(RTLD_DEFAULT, "ray_group");
@@ -131,32 +183,12 @@ int rfx_host_bind(void) {
 }
 
 obj_p rfx_host_fn(const char *name) {
-    static const struct { const char *n; int f; int type; int attrs; } T[] = {
-        {"sum", F_SUM, RFX_TYPE_UNARY, RFX_FN_AGGR}, {"avg", F_AVG, RFX_TYPE_UNARY, RFX_FN_AGGR}, {"min", F_MIN, RFX_TYPE_UNARY, RFX_FN_AGGR},
-        {"max", F_MAX, RFX_TYPE_UNARY, RFX_FN_AGGR}, {"count", F_COUNT, RFX_TYPE_UNARY, RFX_FN_AGGR}, {"first", F_FIRST, RFX_TYPE_UNARY, RFX_FN_AGGR},
-        {"==", F_EQ, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"!=", F_NE, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"<", F_LT, RFX_TYPE_BINARY, RFX_FN_ATOMIC},
-        {">", F_GT, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"<=", F_LE, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {">=", F_GE, RFX_TYPE_BINARY, RFX_FN_ATOMIC},
-        {"and", F_AND, RFX_TYPE_VARY, RFX_FN_SPECIAL_FORM}, {"or", F_OR, RFX_TYPE_VARY, RFX_FN_SPECIAL_FORM}, {"select", F_SELECT, RFX_TYPE_UNARY, 0},
-        {"+", F_ADD, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"-", F_SUB, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"*", F_MUL, RFX_TYPE_BINARY, RFX_FN_ATOMIC},
-        {"div", F_FDIV, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"/", F_DIV, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"%", F_MOD, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"xbar", F_XBAR, RFX_TYPE_BINARY, RFX_FN_ATOMIC}, {"update", F_UPDATE, RFX_TYPE_UNARY, 0},
-        {"med", F_MED, RFX_TYPE_UNARY, RFX_FN_AGGR}, {"dev", F_DEV, RFX_TYPE_UNARY, RFX_FN_AGGR},
-        {"iasc", F_IASC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"idesc", F_IDESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"asc", F_ASC, RFX_TYPE_UNARY, RFX_FN_NONE},
-        {"desc", F_DESC, RFX_TYPE_UNARY, RFX_FN_NONE}, {"rank", F_RANK, RFX_TYPE_UNARY, RFX_FN_NONE}, {"xasc", F_XASC, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"xdesc", F_XDESC, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"asof-join", F_AJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"bin", F_BIN, RFX_TYPE_BINARY, RFX_FN_NONE}, {"binr", F_BINR, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"window-join", F_WJ, RFX_TYPE_VARY, RFX_FN_NONE}, {"window-join1", F_WJ1, RFX_TYPE_VARY, RFX_FN_NONE}, {"last", F_LAST, RFX_TYPE_UNARY, RFX_FN_AGGR},
-        {"distinct", F_DISTINCT, RFX_TYPE_UNARY, RFX_FN_NONE}, {"find", F_FIND, RFX_TYPE_BINARY, RFX_FN_NONE}, {"in", F_IN, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"sect", F_SECT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"except", F_EXCEPT, RFX_TYPE_BINARY, RFX_FN_NONE}, {"union", F_UNION, RFX_TYPE_BINARY, RFX_FN_NONE},
-        {"xrank", F_XRANK, RFX_TYPE_BINARY, RFX_FN_NONE}, {"floor", F_FLOOR, RFX_TYPE_UNARY, RFX_FN_ATOMIC}, {"ceil", F_CEIL, RFX_TYPE_UNARY, RFX_FN_ATOMIC},
-        {"round", F_ROUND, RFX_TYPE_UNARY, RFX_FN_ATOMIC}, {"neg", F_NEG, RFX_TYPE_UNARY, RFX_FN_ATOMIC},
-        {"filter", F_FILTER, RFX_TYPE_BINARY, RFX_FN_NONE}, {"take", F_TAKE, RFX_TYPE_BINARY, RFX_FN_NONE}, {"reverse", F_REVERSE, RFX_TYPE_UNARY, RFX_FN_NONE},
-        {"as", F_AS, RFX_TYPE_BINARY, RFX_FN_NONE}};
     rfx_host_bind();
-    for (size_t i = 0; i < sizeof(T) / sizeof(T[0]); i++)
-        if (strcmp(T[i].n, name) == 0) {
-            obj_p o = rfx_host_i64((int64_t)(intptr_t)OUR_FN[T[i].f]);
-            o->type = (int8_t)T[i].type; /* function objects carry the POSITIVE type code (core/env.c:66-74) */
-            o->attrs = (uint8_t)T[i].attrs;
+    for (int f = 0; f < F_N; f++)
+        if (VERB[f].name && strcmp(VERB[f].name, name) == 0) {
+            obj_p o = rfx_host_i64((int64_t)(intptr_t)VERB[f].ours);
+            o->type = (int8_t)VERB[f].type; /* function objects carry the POSITIVE type code (core/env.c:66-74) */
+            o->attrs = (uint8_t)VERB[f].attrs;
             return o;
         }
     return NULL;
@@ -188,7 +220,7 @@ static int fn_id(obj_p o) {
     if (!o || (o->type != RFX_TYPE_UNARY && o->type != RFX_TYPE_BINARY && o->type != RFX_TYPE_VARY)) return -1;
     void *p = (void *)(intptr_t)o->i64;
     for (int i = 0; i < F_N; i++)
-        if ((OUR_FN[i] && p == OUR_FN[i]) || (H.f[i] && p == H.f[i])) return i;
+        if ((VERB[i].ours && p == VERB[i].ours) || (H.f[i] && p == H.f[i])) return i;
     return -1;
 }
 

@@ -8,37 +8,42 @@ int rfx_last_asof_on_gpu(void) { return g_last_asof_gpu; }
 static obj_p asof_host(obj_p *x, int64_t n, const char *why) {
     g_last_asof_gpu = 0;
     g_asof_handed = 1;
-    snprintf(g_err, sizeof(g_err), "asof_join: handed to the host (%s)", why);
-    if (H.bound == 1 && H.f[F_AJ]) return HOST_CALL(((rfx_vary_f)H.f[F_AJ])(x, n));
-    char b[256];
-    snprintf(b, sizeof(b), "asof_join: not covered by the MI355X path (%s) and no host function to delegate to", why);
-    return fail(b);
+    return hand_off(F_AJ, NULL, 0, 0, x, n, why);
 }
 static int asof_time_type(obj_p c) { return c->type == RFX_TYPE_I64 || c->type == RFX_TYPE_TIMESTAMP || IS_I32_FAMILY(c->type); }
+/* the key tuple of asof-join and of the window joins -- the equality keys' names and, last, the time column's -- looked up in both tables: why the device
+ * does not take it, or NULL with the columns in lk / rk / *ltime / *rtime.  An asof column is an 8-byte or a 4-byte integer, a window column a 4-byte one */
+static const char *join_key_tuple(obj_p ksyms, obj_p lt, obj_p rt, int window, obj_p *lk, obj_p *rk, obj_p *ltime, obj_p *rtime) {
+    if (ksyms->len < 2) return "fewer than two key names";
+    if (is_parted_table(lt) || is_parted_table(rt)) return "parted table";
+    const int nk = (int)ksyms->len - 1; /* the equality keys; the last name is the time column */
+    if (nk > RFX_MAX_KEYS) return "more than 8 equality keys";
+    *ltime = table_col(lt, RFX_AS_I64(ksyms)[nk]);
+    *rtime = table_col(rt, RFX_AS_I64(ksyms)[nk]);
+    if (!*ltime || !*rtime) return window ? "window column missing from a table" : "asof column missing from a table";
+    if ((*ltime)->type != (*rtime)->type) return window ? "window columns of different types" : "asof columns of different types";
+    /* (an F64 asof column, an I64 / TIMESTAMP window column the reference reads through AS_I32: DESIGN.md, reference defects observed -- the host's) */
+    if (window ? !IS_I32_FAMILY((*ltime)->type) : !asof_time_type(*ltime)) return window ? "window column type" : "asof column type";
+    for (int i = 0; i < nk; i++) {
+        lk[i] = table_col(lt, RFX_AS_I64(ksyms)[i]);
+        rk[i] = table_col(rt, RFX_AS_I64(ksyms)[i]);
+        if (!lk[i] || !rk[i] || lk[i]->type <= 0 || rk[i]->type <= 0 || col_ctype(lk[i]) != RFX_I64 || col_ctype(rk[i]) != RFX_I64 || lk[i]->type != rk[i]->type)
+            return "equality key is not an 8-byte integer column of both tables";
+    }
+    return NULL;
+}
 static obj_p asof_impl(obj_p *x, int64_t n) {
     rfx_host_bind();
     g_last_asof_gpu = 0;
     /* the reference's own errors (arity, types, one key name, no such asof column, asof columns of two types) are the reference's to word */
     if (n != 3 || !x || !x[0] || !x[1] || !x[2]) return asof_host(x, n, "expected (keys, left table, right table)");
     if (x[0]->type != RFX_TYPE_SYMBOL || x[1]->type != RFX_TYPE_TABLE || x[2]->type != RFX_TYPE_TABLE) return asof_host(x, n, "expected (symbol vector, table, table)");
-    obj_p ksyms = x[0], lt = x[1], rt = x[2];
-    if (ksyms->len < 2) return asof_host(x, n, "fewer than two key names");
-    if (is_parted_table(lt) || is_parted_table(rt)) return asof_host(x, n, "parted table");
+    obj_p ksyms = x[0], lt = x[1], rt = x[2], lk[RFX_MAX_KEYS], rk[RFX_MAX_KEYS], ltime = NULL, rtime = NULL;
+    const char *why = join_key_tuple(ksyms, lt, rt, 0, lk, rk, &ltime, &rtime);
+    if (why) return asof_host(x, n, why);
     obj_p lnames = RFX_AS_LIST(lt)[0], lcols = RFX_AS_LIST(lt)[1], rnames = RFX_AS_LIST(rt)[0], rcols = RFX_AS_LIST(rt)[1];
     const int64_t nl = lcols->len ? RFX_AS_LIST(lcols)[0]->len : 0, nr = rcols->len ? RFX_AS_LIST(rcols)[0]->len : 0;
     const int nk = (int)ksyms->len - 1; /* the equality keys; the last name is the asof column */
-    if (nk > RFX_MAX_KEYS) return asof_host(x, n, "more than 8 equality keys");
-    obj_p ltime = table_col(lt, RFX_AS_I64(ksyms)[nk]), rtime = table_col(rt, RFX_AS_I64(ksyms)[nk]);
-    if (!ltime || !rtime) return asof_host(x, n, "asof column missing from a table");
-    if (ltime->type != rtime->type) return asof_host(x, n, "asof columns of different types");
-    if (!asof_time_type(ltime)) return asof_host(x, n, "asof column type"); /* (F64 among them: DESIGN.md, reference defects observed) */
-    obj_p lk[RFX_MAX_KEYS], rk[RFX_MAX_KEYS];
-    for (int i = 0; i < nk; i++) {
-        lk[i] = table_col(lt, RFX_AS_I64(ksyms)[i]);
-        rk[i] = table_col(rt, RFX_AS_I64(ksyms)[i]);
-        if (!lk[i] || !rk[i] || lk[i]->type <= 0 || rk[i]->type <= 0 || col_ctype(lk[i]) != RFX_I64 || col_ctype(rk[i]) != RFX_I64 || lk[i]->type != rk[i]->type)
-            return asof_host(x, n, "equality key is not an 8-byte integer column of both tables");
-    }
     /* every other column travels as 8 bytes.  The exemption is by NAME: only the column the asof symbol resolves to is never gathered (the result's
      * is the left table's own object); the same 4-byte vector under a second name -- (table [s t qt] (list S T T)) -- is a passenger like any other */
     const int64_t tsym = RFX_AS_I64(ksyms)[nk];
@@ -65,7 +70,7 @@ static obj_p asof_impl(obj_p *x, int64_t n) {
     /* (a 4-byte asof column is resident as its widened copy, rfx_hip_widen_i32: order and nulls survive) */
     if (resident(ltime, 0, &dlt) != RFX_OK || resident(rtime, 0, &drt) != RFX_OK) return fail_hip("column upload");
     void *ids = NULL;
-    if (sort_tmp(&ids, (size_t)nl * 8) != RFX_OK) return asof_host(x, n, "device memory");
+    if (op_scratch(&ids, (size_t)nl * 8) != RFX_OK) return asof_host(x, n, "device memory");
     int collision = 0;
     const int rc = rfx_exec_asof_index(g_x, dlk, drk, nk, (const int64_t *)dlt, (const int64_t *)drt, nl, nr, (int64_t *)ids, &collision);
     if (rc != RFX_OK && collision) return asof_host(x, n, "row-hash collision between two key tuples");
@@ -90,11 +95,7 @@ rfx_obj_p rfx_asof_join(rfx_obj_p *x, int64_t n) {
 
 static obj_p bin_host(int f, obj_p x, obj_p y, const char *why) {
     g_last_asof_gpu = 0;
-    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
-    if (H.bound == 1 && H.f[f]) return HOST_CALL(((rfx_binary_f)H.f[f])(x, y));
-    char b[256];
-    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%s) and no host function to delegate to", HOST_FN[f] + 4, why);
-    return fail(b);
+    return hand_off_xy(f, NULL, x, y, why);
 }
 static obj_p bin_impl(int right, obj_p x, obj_p y) {
     rfx_host_bind();
@@ -110,7 +111,7 @@ static obj_p bin_impl(int right, obj_p x, obj_p y) {
     const void *dx = NULL, *dy = NULL;
     void *dout = NULL;
     if (resident(x, 0, &dx) != RFX_OK || resident(y, 0, &dy) != RFX_OK) return fail_hip("column upload");
-    if (sort_tmp(&dout, (size_t)ny * 8) != RFX_OK) return bin_host(f, x, y, "device memory");
+    if (op_scratch(&dout, (size_t)ny * 8) != RFX_OK) return bin_host(f, x, y, "device memory");
     if (rfx_exec_bin(g_x, (const int64_t *)dx, nx, (const int64_t *)dy, ny, right, (int64_t *)dout) != RFX_OK) return fail(rfx_exec_last_error(g_x));
     obj_p out = H.vector(RFX_TYPE_I64, ny);
     if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), dout, (size_t)ny * 8) != RFX_OK) {
@@ -120,15 +121,5 @@ static obj_p bin_impl(int right, obj_p x, obj_p y) {
     g_last_asof_gpu = 1;
     return out;
 }
-rfx_obj_p rfx_bin(rfx_obj_p x, rfx_obj_p y) {
-    op_begin();
-    obj_p r = bin_impl(0, x, y);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_binr(rfx_obj_p x, rfx_obj_p y) {
-    op_begin();
-    obj_p r = bin_impl(1, x, y);
-    op_end();
-    return r;
-}
+OP2(rfx_bin, bin_impl(0, x, y))
+OP2(rfx_binr, bin_impl(1, x, y))

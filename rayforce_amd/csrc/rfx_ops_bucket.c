@@ -1,18 +1,15 @@
 /* rfx_ops_bucket.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own).
  * The bucket verbs as built-ins of their own: xrank (ray_xrank, core/order.c:598-649), xbar (ray_xbar, core/math.c:1635-1782,2442), within (ray_within,
  * core/items.c:848-872), floor / ceil / round (core/math.c:2047-2117,2430-2432), neg (ray_neg, core/order.c:445-497) on the device (rfx_bucket.hip through
- * rfx_exec_bucket.c).  The family's hand-off rule: a shape the device does not take is the host's own verb when a host is bound, else an error object
+ * rfx_exec_bucket.c).
+ * The hand-off is the shared one (hand_off, rfx_ops_plan.c): a shape the device does not take is the host's own verb when a host is bound, else an error object
  * naming the reason (also in rfx_ops_last_error()).  Every result is a fresh host vector with the reference's result type; nothing is written in place. */
 static int g_last_bucket_gpu = 0;
 int rfx_last_bucket_on_gpu(void) { return g_last_bucket_gpu; }
 
 static obj_p bucket_host(int f, obj_p x, obj_p y, const char *why) {
     g_last_bucket_gpu = 0;
-    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
-    if (H.bound == 1 && H.f[f]) return y ? HOST_CALL(((rfx_binary_f)H.f[f])(x, y)) : HOST_CALL(((rfx_unary_f)H.f[f])(x));
-    char b[256];
-    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%s) and no host function to delegate to", HOST_FN[f] + 4, why);
-    return fail(b);
+    return hand_off_xy(f, NULL, x, y, why);
 }
 static int bucket_is_device(obj_p v) { return v->mmod == RFX_MMOD_DEVICE; }
 
@@ -43,7 +40,7 @@ static obj_p xrank_impl(obj_p v, obj_p nobj) {
     const void *dv = NULL;
     void *d0 = NULL;
     if (!attrs && resident(v, 0, &dv) != RFX_OK) return fail_hip("column upload");
-    int rc = sort_tmp(&d0, (size_t)n * 8);
+    int rc = op_scratch(&d0, (size_t)n * 8);
     if (rc == RFX_OK) rc = rfx_exec_xrank(g_x, dv, col_ctype(v), attrs, n, nb, (int64_t *)d0);
     if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return bucket_host(F_XRANK, v, nobj, rc == RFX_ENOMEM ? "device memory" : "more rows than the device sort takes");
     if (rc != RFX_OK) return fail_hip("xrank");
@@ -90,13 +87,10 @@ static obj_p bucket_run(bucket_arg_t *A, int8_t out_type, size_t esz, int64_t n,
     g_last_bucket_gpu = 1;
     return out;
 }
-/* the shards' pieces of a vector operand (uploaded if need be) */
+/* the shards' pieces of a vector operand (uploaded if need be); a piece that is missing goes to the planner as the NULL it is */
 static int bucket_operand(obj_p v, const void **pieces) {
-    const void *d = NULL;
-    int rc = resident(v, 0, &d);
-    if (rc != RFX_OK) return rc;
-    for (int s = 0; s < g_nshards; s++) pieces[s] = shard_piece(d, s);
-    return RFX_OK;
+    const int rc = col_pieces(v, pieces);
+    return rc == COL_PIECE_MISSING ? RFX_OK : rc;
 }
 
 static uint64_t bucket_atom_bits(obj_p a) {
@@ -141,7 +135,7 @@ static obj_p round_impl(int op, int f, obj_p x) {
     A.verb = 1;
     A.op = op;
     if (bucket_operand(x, A.xs) != RFX_OK) return fail_hip("column upload");
-    return bucket_run(&A, RFX_TYPE_F64, 8, x->len, HOST_FN[f] + 4);
+    return bucket_run(&A, RFX_TYPE_F64, 8, x->len, VERB[f].host + 4);
 }
 static obj_p neg_impl(obj_p x) {
     rfx_host_bind();
@@ -173,24 +167,10 @@ static obj_p within_impl(obj_p x, obj_p y) {
     return bucket_run(&A, RFX_TYPE_B8, 1, x->len, "within");
 }
 
-#define BUCKET_UNARY(name, call)       \
-    rfx_obj_p name(rfx_obj_p x) {      \
-        op_begin();                    \
-        obj_p r = call;                \
-        op_end();                      \
-        return r;                      \
-    }
-#define BUCKET_BINARY(name, call)                  \
-    rfx_obj_p name(rfx_obj_p x, rfx_obj_p y) {     \
-        op_begin();                                \
-        obj_p r = call;                            \
-        op_end();                                  \
-        return r;                                  \
-    }
-BUCKET_BINARY(rfx_xrank, xrank_impl(x, y))
-BUCKET_BINARY(rfx_xbar, xbar_impl(x, y))
-BUCKET_BINARY(rfx_within, within_impl(x, y))
-BUCKET_UNARY(rfx_floor, round_impl(RFX_ROUND_FLOOR, F_FLOOR, x))
-BUCKET_UNARY(rfx_ceil, round_impl(RFX_ROUND_CEIL, F_CEIL, x))
-BUCKET_UNARY(rfx_round, round_impl(RFX_ROUND_ROUND, F_ROUND, x))
-BUCKET_UNARY(rfx_neg, neg_impl(x))
+OP2(rfx_xrank, xrank_impl(x, y))
+OP2(rfx_xbar, xbar_impl(x, y))
+OP2(rfx_within, within_impl(x, y))
+OP1(rfx_floor, round_impl(RFX_ROUND_FLOOR, F_FLOOR, x))
+OP1(rfx_ceil, round_impl(RFX_ROUND_CEIL, F_CEIL, x))
+OP1(rfx_round, round_impl(RFX_ROUND_ROUND, F_ROUND, x))
+OP1(rfx_neg, neg_impl(x))

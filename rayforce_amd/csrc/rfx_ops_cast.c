@@ -1,6 +1,7 @@
 /* rfx_ops_cast.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own).
  * `as` as a built-in of its own (ray_cast_obj, core/compose.c:42-68 -> cast_obj, core/rayforce.c:2312-2831): a vector of one of the nine numeric and
- * temporal types cast to another of them on the device (rfx_cast.hip through rfx_exec_cast.c).  The family's hand-off rule: a shape the device does not
+ * temporal types cast to another of them on the device (rfx_cast.hip through rfx_exec_cast.c).
+ * The hand-off is the shared one (hand_off, rfx_ops_plan.c): a shape the device does not
  * take is the host's own verb when a host is bound, else an error object naming the reason (also in rfx_ops_last_error()).  A converted result is a
  * fresh host vector of the target type, attribute byte 0; the same type is a clone of the argument, as the reference answers it. */
 static int g_last_cast_gpu = 0;
@@ -8,11 +9,7 @@ int rfx_last_cast_on_gpu(void) { return g_last_cast_gpu; }
 
 static obj_p cast_host(obj_p t, obj_p x, const char *why) {
     g_last_cast_gpu = 0;
-    snprintf(g_err, sizeof(g_err), "as: handed to the host (%s)", why);
-    if (H.bound == 1 && H.f[F_AS]) return HOST_CALL(((rfx_binary_f)H.f[F_AS])(t, x));
-    char b[256];
-    snprintf(b, sizeof(b), "as: not covered by the MI355X path (%s) and no host function to delegate to", why);
-    return fail(b);
+    return hand_off_xy(F_AS, "as", t, x, why); /* (the host's symbol is ray_cast_obj: the verb's own name is passed in) */
 }
 /* the nine types by either spelling of their names (the atom's 'i32 is flipped to the vector's 'I32 when the source is a vector, core/compose.c:53-65);
  * 0: another name */
@@ -25,37 +22,6 @@ static int cast_type_of(int64_t sym) {
     for (size_t i = 0; i < sizeof(T) / sizeof(T[0]); i++)
         if (strcmp(s, T[i].atom) == 0 || strcmp(s, T[i].vec) == 0) return T[i].type;
     return 0;
-}
-static size_t cast_cell_bytes(int type) {
-    switch (type) {
-        case RFX_TYPE_B8: case RFX_TYPE_U8: return 1;
-        case RFX_TYPE_I16: return 2;
-        case RFX_TYPE_I32: case RFX_TYPE_DATE: case RFX_TYPE_TIME: return 4;
-        case RFX_TYPE_I64: case RFX_TYPE_TIMESTAMP: case RFX_TYPE_F64: return 8;
-        default: return 0;
-    }
-}
-/* a U8 / I16 vector's cells as they are, every shard its row range, for this call only (the residency cache keeps 8-byte, widened 4-byte and B8 columns);
- * released by qtmp_release */
-static int cast_raw_pieces(obj_p v, size_t esz, const void **pieces) {
-    if (g_nqtmp >= (int)(sizeof(g_qtmp) / sizeof(g_qtmp[0]))) return RFX_ELIMIT;
-    void *devs[RFX_MAX_SHARDS];
-    int rc = shards_alloc(devs, v->len, esz, 0);
-    if (rc != RFX_OK) return rc;
-    memset(&g_qtmp[g_nqtmp], 0, sizeof(g_qtmp[0]));
-    for (int s = 0; s < g_nshards; s++) g_qtmp[g_nqtmp].d[s] = devs[s];
-    g_nqtmp++;
-    for (int s = 0; s < g_nshards && rc == RFX_OK; s++) {
-        int64_t r0, n;
-        rfx_exec_split(v->len, g_nshards, s, &r0, &n);
-        pieces[s] = devs[s];
-        if (n <= 0) continue;
-        if (g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctxs[s]);
-        rc = rfx_hip_h2d_pipelined(g_ctxs[s], devs[s], (const char *)RFX_AS_RAW(v) + (size_t)r0 * esz, (size_t)n * esz);
-    }
-    if (g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctx);
-    g_stat[ST_UPLOADS]++;
-    return rc;
 }
 typedef struct {
     int32_t src_type, dst_type;
@@ -76,7 +42,7 @@ static obj_p cast_impl(obj_p t, obj_p x) {
     const int dst = cast_type_of(t->i64);
     if (!dst) return cast_host(t, x, "a type name outside the nine numeric and temporal types");
     if (x->type < 0) return cast_host(t, x, "an atom");
-    const size_t ssz = cast_cell_bytes(x->type), dsz = cast_cell_bytes(dst);
+    const size_t ssz = cell_bytes(x->type), dsz = cell_bytes(dst);
     if (!ssz) return cast_host(t, x, "not a vector of the nine numeric and temporal types");
     const int device = x->mmod == RFX_MMOD_DEVICE;
     if (device && ssz != 8 && x->type != RFX_TYPE_B8) return cast_host(t, x, "a device column that is not I64 / F64 / TIMESTAMP / B8");
@@ -96,22 +62,18 @@ static obj_p cast_impl(obj_p t, obj_p x) {
     A.src_type = x->type;
     A.dst_type = dst;
     int rc;
-    if (x->type == RFX_TYPE_U8 || x->type == RFX_TYPE_I16) rc = cast_raw_pieces(x, ssz, A.xs);
+    if (x->type == RFX_TYPE_U8 || x->type == RFX_TYPE_I16) rc = raw_pieces(x, ssz, A.xs);
     else {
-        const void *d = NULL;
-        rc = resident(x, 0, &d);
-        for (int s = 0; s < g_nshards && rc == RFX_OK; s++)
-            if (!(A.xs[s] = shard_piece(d, s))) rc = RFX_ELIMIT;
+        rc = col_pieces(x, A.xs);
+        if (rc == COL_PIECE_MISSING) rc = RFX_ELIMIT;
         if (!device && IS_I32_FAMILY(x->type)) A.src_type |= RFX_CAST_WIDENED; /* (the resident copy of a 4-byte column is its widened image) */
     }
     if (rc != RFX_OK) {
-        qtmp_release();
         if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return cast_host(t, x, rc == RFX_ENOMEM ? "device memory" : "a column the residency cache does not take");
         return fail_hip("column upload");
     }
     obj_p out = H.vector((int8_t)dst, n);
     rc = map_shards(out, dsz, cast_piece, &A);
-    qtmp_release();
     if (rc != RFX_OK) {
         H.drop(out);
         if (rc == RFX_ENOMEM) return cast_host(t, x, "device memory");
@@ -123,9 +85,4 @@ static obj_p cast_impl(obj_p t, obj_p x) {
     g_last_cast_gpu = 1;
     return out;
 }
-rfx_obj_p rfx_as(rfx_obj_p type_name, rfx_obj_p x) {
-    op_begin();
-    obj_p r = cast_impl(type_name, x);
-    op_end();
-    return r;
-}
+OP2(rfx_as, cast_impl(x, y))

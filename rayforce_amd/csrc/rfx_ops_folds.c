@@ -166,12 +166,7 @@ static obj_p fold_mapgroup(int f, int kind, obj_p x) {
 out:
     for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
     ntmp = 0;
-    if (H.bound == 1 && H.f[f]) res = HOST_CALL(((rfx_unary_f)H.f[f])(x));
-    else {
-        char b[256];
-        snprintf(b, sizeof(b), "aggregate over a MAPGROUP pair: not covered by the MI355X path (%s) and no host function to delegate to", why ? why : "unsupported");
-        res = fail(b);
-    }
+    res = hand_off(f, "aggregate over a MAPGROUP pair", HAND_QUIET, 1, &x, 1, why ? why : "unsupported");
 done:
     for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
     return res;
@@ -370,12 +365,7 @@ static obj_p group_impl(obj_p keys) {
     ix[6] = firsts;
     return res;
 }
-rfx_obj_p rfx_group(rfx_obj_p keys) {
-    op_begin();
-    obj_p r = group_impl(keys);
-    op_end();
-    return r;
-}
+OP1(rfx_group, group_impl(x))
 
 /* scalar aggregates of a vector or of a lazy MAPFILTER (val, ids) pair (core/filter.c:29-49, core/math.c:1874-1890) */
 static obj_p fold_impl(int f, int kind, obj_p x) {
@@ -449,21 +439,15 @@ static obj_p fold_impl(int f, int kind, obj_p x) {
     if (rfx_hip_filter_aggr_host(g_ctx, NULL, 0, RFX_AND, &a, 1, x->len, &v, NULL) != RFX_OK) return fail_hip("filter_aggr");
     return value_atom(&v);
 }
-static obj_p fold_op(int f, int kind, obj_p x) {
-    op_begin();
-    obj_p r = fold_impl(f, kind, x);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_sum(rfx_obj_p x) { return fold_op(F_SUM, RFX_AGG_SUM, x); }
-rfx_obj_p rfx_avg(rfx_obj_p x) { return fold_op(F_AVG, RFX_AGG_AVG, x); }
-rfx_obj_p rfx_min(rfx_obj_p x) { return fold_op(F_MIN, RFX_AGG_MIN, x); }
-rfx_obj_p rfx_max(rfx_obj_p x) { return fold_op(F_MAX, RFX_AGG_MAX, x); }
-rfx_obj_p rfx_count(rfx_obj_p x) { return fold_op(F_COUNT, RFX_AGG_COUNT, x); }
-rfx_obj_p rfx_first(rfx_obj_p x) { return fold_op(F_FIRST, RFX_AGG_FIRST, x); }
+OP1(rfx_sum, fold_impl(F_SUM, RFX_AGG_SUM, x))
+OP1(rfx_avg, fold_impl(F_AVG, RFX_AGG_AVG, x))
+OP1(rfx_min, fold_impl(F_MIN, RFX_AGG_MIN, x))
+OP1(rfx_max, fold_impl(F_MAX, RFX_AGG_MAX, x))
+OP1(rfx_count, fold_impl(F_COUNT, RFX_AGG_COUNT, x))
+OP1(rfx_first, fold_impl(F_FIRST, RFX_AGG_FIRST, x))
 /* ray_last: a vector's last cell (at_idx(x, len - 1), core/items.c:1112-1114), a MAPFILTER pair's last collected cell -- positional, null or not -- and per
  * group of a MAPGROUP pair the last non-null cell (aggr_last with one chunk, core/aggr.c:851-930) */
-rfx_obj_p rfx_last(rfx_obj_p x) { return fold_op(F_LAST, RFX_AGG_LAST, x); }
+OP1(rfx_last, fold_impl(F_LAST, RFX_AGG_LAST, x))
 
 /* ---- (med x): ray_med (core/math.c:2529-2626) -- an I64 vector or a MAPFILTER over one (filter_collect, then the scalar rule), a MAPGROUP over I64 /
  * TIMESTAMP / F64 values (aggr_med: the grouped rule) -- exact medians on the device (rfx_median.hip).  (ray_med itself reaches neither lazy arm: its
@@ -471,12 +455,9 @@ rfx_obj_p rfx_last(rfx_obj_p x) { return fold_op(F_LAST, RFX_AGG_LAST, x); }
  * medians those arms compute.  rfx_select follows ray_select and leaves med under by: / where: to the host.)  The MAPGROUP's rows are counted in their group
  * straight from the index: IDS through its id column, SHIFT through its key table and source column (gathered by the filter ids, as fold_mapgroup does).
  * Everything else -- other types, parted / window indexes, sharded columns -- is the host's own ray_med. */
-static obj_p med_host(obj_p x, const char *why) {
-    if (H.bound == 1 && H.f[F_MED]) return HOST_CALL(((rfx_unary_f)H.f[F_MED])(x));
-    char b[256];
-    snprintf(b, sizeof(b), "med: not covered by the MI355X path (%s) and no host ray_med to delegate to", why);
-    return fail(b);
-}
+/* (the shared hand_off in the folds' wording: nothing into rfx_ops_last_error() before the host is called, the error names the host's symbol) */
+static obj_p fold_host(int f, obj_p x, const char *why) { return hand_off(f, NULL, HAND_QUIET | HAND_NAMES_SYMBOL, 1, &x, 1, why); }
+static obj_p med_host(obj_p x, const char *why) { return fold_host(F_MED, x, why); }
 static obj_p med_impl(obj_p x) {
     rfx_host_bind();
     if (!x) return fail("med: null argument");
@@ -563,12 +544,7 @@ done:
     for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
     return res;
 }
-rfx_obj_p rfx_med(rfx_obj_p x) {
-    op_begin();
-    obj_p r = med_impl(x);
-    op_end();
-    return r;
-}
+OP1(rfx_med, med_impl(x))
 
 /* ---- (dev x): ray_dev (core/math.c:2628-2699) -- an I64 / F64 vector or a MAPFILTER over one (filter_collect, then the two passes of the scalar rule), a
  * MAPGROUP over I64 / TIMESTAMP / F64 values (aggr_dev: the grouped rule, core/aggr.c:2250-2350,2864-2929) -- on the device (rfx_lastdev.hip).  (ray_dev
@@ -576,12 +552,7 @@ rfx_obj_p rfx_med(rfx_obj_p x) {
  * function as its own `dev` aggregate gets the deviations those arms compute.  rfx_select follows ray_select and leaves dev under by: / where: to the
  * host.)  The MAPGROUP's value and key columns are prepared as fold_mapgroup prepares them; the three sums per group ride through the planner's group-by
  * (rfx_exec_group_dev).  Everything else -- other types, parted / window indexes, sharded columns -- is the host's own ray_dev. */
-static obj_p dev_host(obj_p x, const char *why) {
-    if (H.bound == 1 && H.f[F_DEV]) return HOST_CALL(((rfx_unary_f)H.f[F_DEV])(x));
-    char b[256];
-    snprintf(b, sizeof(b), "dev: not covered by the MI355X path (%s) and no host ray_dev to delegate to", why);
-    return fail(b);
-}
+static obj_p dev_host(obj_p x, const char *why) { return fold_host(F_DEV, x, why); }
 static obj_p dev_impl(obj_p x) {
     rfx_host_bind();
     if (!x) return fail("dev: null argument");
@@ -676,9 +647,4 @@ done:
     for (int i = 0; i < ntmp; i++) rfx_hip_free(g_ctx, tmp[i]);
     return res;
 }
-rfx_obj_p rfx_dev(rfx_obj_p x) {
-    op_begin();
-    obj_p r = dev_impl(x);
-    op_end();
-    return r;
-}
+OP1(rfx_dev, dev_impl(x))

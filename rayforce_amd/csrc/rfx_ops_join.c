@@ -379,9 +379,4 @@ static obj_p at_impl(obj_p col, obj_p ids) {
     if (!ok) { H.drop(out); return fail_hip("gather"); }
     return out;
 }
-rfx_obj_p rfx_at(rfx_obj_p col, rfx_obj_p ids) {
-    op_begin();
-    obj_p r = at_impl(col, ids);
-    op_end();
-    return r;
-}
+OP2(rfx_at, at_impl(x, y))

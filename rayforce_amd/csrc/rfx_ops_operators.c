@@ -34,6 +34,54 @@ static int map_shards(obj_p out, size_t esz, piece_fn fn, void *arg) {
     rfx_hip_ctx_bind_thread(g_ctx);
     return rc;
 }
+/* ---- one operand path for the verb families ---- */
+/* a resident column (uploaded if need be) as the shards' pieces: pieces[s] for every shard.  resident()'s error, or -- the column is resident but a shard's
+ * piece is not in the call's column table -- COL_PIECE_MISSING with NULL in that piece's place: a limit of the call to the sort, the cast and filter,
+ * nothing to the bucket verbs, whose planner takes the NULL */
+#define COL_PIECE_MISSING 1
+static int col_pieces(obj_p c, const void **pieces) {
+    const void *d = NULL;
+    int rc = resident(c, 0, &d);
+    for (int s = 0; s < g_nshards && rc == RFX_OK; s++) pieces[s] = shard_piece(d, s);
+    for (int s = 0; s < g_nshards && rc == RFX_OK; s++)
+        if (!pieces[s]) rc = COL_PIECE_MISSING;
+    return rc;
+}
+/* a U8 / I16 vector's cells as they are, every shard its row range, for this call only (the residency cache keeps 8-byte, widened 4-byte and B8 columns):
+ * the call's device scratch, released by op_end().  Scratch that does not fit (RFX_ELIMIT: the list is full, RFX_ENOMEM) leaves pieces[0] NULL; a failed
+ * copy leaves the pieces where they are */
+static int raw_pieces(obj_p v, size_t esz, const void **pieces) {
+    int rc = RFX_OK;
+    for (int s = 0; s < g_nshards && rc == RFX_OK; s++) {
+        int64_t n;
+        void *d = NULL;
+        rfx_exec_split(v->len, g_nshards, s, NULL, &n);
+        if (g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctxs[s]);
+        rc = op_scratch_on(s, &d, (size_t)(n > 0 ? n : 1) * esz);
+        pieces[s] = d;
+    }
+    if (rc != RFX_OK) pieces[0] = NULL;
+    for (int s = 0; s < g_nshards && rc == RFX_OK; s++) {
+        int64_t r0, n;
+        rfx_exec_split(v->len, g_nshards, s, &r0, &n);
+        if (n <= 0) continue;
+        if (g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctxs[s]);
+        rc = rfx_hip_h2d_pipelined(g_ctxs[s], (void *)pieces[s], (const char *)RFX_AS_RAW(v) + (size_t)r0 * esz, (size_t)n * esz);
+    }
+    if (g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctx);
+    if (pieces[0]) g_stat[ST_UPLOADS]++;
+    return rc;
+}
+/* bytes of one cell of a vector type the sort's vector verbs and the cast take (0: another type) */
+static size_t cell_bytes(int type) {
+    switch (type) {
+        case RFX_TYPE_B8: case RFX_TYPE_U8: return 1;
+        case RFX_TYPE_I16: return 2;
+        case RFX_TYPE_I32: case RFX_TYPE_DATE: case RFX_TYPE_TIME: return 4;
+        case RFX_TYPE_I64: case RFX_TYPE_TIMESTAMP: case RFX_TYPE_F64: return 8;
+        default: return 0;
+    }
+}
 typedef struct { rfx_pred_t p; } cmp_arg_t;
 static int cmp_piece(void *arg, int s, int64_t r0, int64_t n, void *d_out) {
     (void)r0;
@@ -97,12 +145,6 @@ static obj_p cmp_impl(int op, obj_p x, obj_p y) {
     if (!ok) { H.drop(out); return fail_hip("cmp_mask"); }
     return out;
 }
-static obj_p cmp_op(int op, obj_p x, obj_p y) {
-    op_begin();
-    obj_p r = cmp_impl(op, x, y);
-    op_end();
-    return r;
-}
 /* ray_add / ray_sub / ray_mul / ray_fdiv / ray_div / ray_mod over an i64 / f64 vector and a vector or atom (binop_map, core/math.c:2280-2345) */
 static obj_p arith_impl(int xop, int fidx, obj_p x, obj_p y) {
     rfx_host_bind();
@@ -154,25 +196,19 @@ static obj_p arith_impl(int xop, int fidx, obj_p x, obj_p y) {
     if (!ok) { if (out) H.drop(out); return fail_hip("eval_expr"); }
     return out;
 }
-static obj_p arith_op(int xop, int fidx, obj_p x, obj_p y) {
-    op_begin();
-    obj_p r = arith_impl(xop, fidx, x, y);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_add(rfx_obj_p x, rfx_obj_p y) { return arith_op(RFX_X_ADD, F_ADD, x, y); }
-rfx_obj_p rfx_sub(rfx_obj_p x, rfx_obj_p y) { return arith_op(RFX_X_SUB, F_SUB, x, y); }
-rfx_obj_p rfx_mul(rfx_obj_p x, rfx_obj_p y) { return arith_op(RFX_X_MUL, F_MUL, x, y); }
-rfx_obj_p rfx_div(rfx_obj_p x, rfx_obj_p y) { return arith_op(RFX_X_FDIV, F_FDIV, x, y); }
-rfx_obj_p rfx_floordiv(rfx_obj_p x, rfx_obj_p y) { return arith_op(RFX_X_DIV, F_DIV, x, y); } /* the reference's `/` (ray_div) */
-rfx_obj_p rfx_mod(rfx_obj_p x, rfx_obj_p y) { return arith_op(RFX_X_MOD, F_MOD, x, y); }      /* `%` (ray_mod) */
+OP2(rfx_add, arith_impl(RFX_X_ADD, F_ADD, x, y))
+OP2(rfx_sub, arith_impl(RFX_X_SUB, F_SUB, x, y))
+OP2(rfx_mul, arith_impl(RFX_X_MUL, F_MUL, x, y))
+OP2(rfx_div, arith_impl(RFX_X_FDIV, F_FDIV, x, y))
+OP2(rfx_floordiv, arith_impl(RFX_X_DIV, F_DIV, x, y)) /* the reference's `/` (ray_div) */
+OP2(rfx_mod, arith_impl(RFX_X_MOD, F_MOD, x, y))      /* `%` (ray_mod) */
 
-rfx_obj_p rfx_eq(rfx_obj_p x, rfx_obj_p y) { return cmp_op(RFX_EQ, x, y); }
-rfx_obj_p rfx_ne(rfx_obj_p x, rfx_obj_p y) { return cmp_op(RFX_NE, x, y); }
-rfx_obj_p rfx_lt(rfx_obj_p x, rfx_obj_p y) { return cmp_op(RFX_LT, x, y); }
-rfx_obj_p rfx_gt(rfx_obj_p x, rfx_obj_p y) { return cmp_op(RFX_GT, x, y); }
-rfx_obj_p rfx_le(rfx_obj_p x, rfx_obj_p y) { return cmp_op(RFX_LE, x, y); }
-rfx_obj_p rfx_ge(rfx_obj_p x, rfx_obj_p y) { return cmp_op(RFX_GE, x, y); }
+OP2(rfx_eq, cmp_impl(RFX_EQ, x, y))
+OP2(rfx_ne, cmp_impl(RFX_NE, x, y))
+OP2(rfx_lt, cmp_impl(RFX_LT, x, y))
+OP2(rfx_gt, cmp_impl(RFX_GT, x, y))
+OP2(rfx_le, cmp_impl(RFX_LE, x, y))
+OP2(rfx_ge, cmp_impl(RFX_GE, x, y))
 
 static obj_p logic_op(int logic, obj_p *x, int64_t n) {
     rfx_host_bind();
@@ -278,7 +314,7 @@ static obj_p sf_logic_impl(int f, obj_p *x, int64_t n) {
     sf_cols_t c;
     memset(&c, 0, sizeof(c));
     obj_p tree = H.vector(RFX_TYPE_LIST, n + 1), tab = NULL, res = NULL;
-    obj_p fo = H.i64((int64_t)(intptr_t)OUR_FN[f]);
+    obj_p fo = H.i64((int64_t)(intptr_t)VERB[f].ours);
     fo->type = RFX_TYPE_VARY;
     RFX_AS_LIST(tree)[0] = fo;
     int ok = 1;
@@ -340,19 +376,10 @@ static obj_p sf_logic_impl(int f, obj_p *x, int64_t n) {
     if (tab) H.drop(tab);
     if (res) return res;
     /* not covered: the host's own special form evaluates the arms */
-    if (H.bound == 1 && H.f[f]) return HOST_CALL(((rfx_vary_f)H.f[f])(x, n));
-    char b[256];
-    snprintf(b, sizeof(b), "and/or (special form): not covered by the MI355X path (%s) and no host function to delegate to", why);
-    return fail(b);
+    return hand_off(f, "and/or (special form)", HAND_QUIET, 0, x, n, why);
 }
-static obj_p sf_logic(int f, obj_p *x, int64_t n) {
-    op_begin();
-    obj_p r = sf_logic_impl(f, x, n);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_and_sf(rfx_obj_p *x, int64_t n) { return sf_logic(F_AND, x, n); }
-rfx_obj_p rfx_or_sf(rfx_obj_p *x, int64_t n) { return sf_logic(F_OR, x, n); }
+OPN(rfx_and_sf, sf_logic_impl(F_AND, x, n))
+OPN(rfx_or_sf, sf_logic_impl(F_OR, x, n))
 
 /* ---- the operators beside rfx_select over the shards (round 5): what the reference parallelises over its pool for every FN_AGGR
  * built-in (aggr_map core/aggr.c:375, unop_fold core/math.c:2176-2231), planned through rfx_exec on every shard ---- */
@@ -476,9 +503,4 @@ static obj_p where_impl(obj_p mask) {
     return out;
 }
 
-rfx_obj_p rfx_where(rfx_obj_p mask) {
-    op_begin();
-    obj_p r = where_impl(mask);
-    op_end();
-    return r;
-}
+OP1(rfx_where, where_impl(x))

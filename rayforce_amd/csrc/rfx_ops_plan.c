@@ -493,6 +493,31 @@ static obj_p refusedn(int f, obj_p *x, int64_t n) {
     if (g_refused_sharded && H.bound == 1 && f >= 0 && f < F_N && H.f[f]) return HOST_CALL(((rfx_vary_f)H.f[f])(x, n));
     return fail_ctx();
 }
+/* The ONE hand-off of the verb families (sort, asof, window, set, bucket, rows, cast, the med / dev and MAPGROUP folds, the and / or special forms): a
+ * shape the device path does not take is the host's own verb when a host is bound -- called by arity: 1 (x[0]), 2 (x[0], x[1]), anything else the
+ * variadic (x, n) -- else an error object naming the reason.  The reason goes into rfx_ops_last_error() first, behind the label (HAND_QUIET: not).
+ * `label` NULL is the host symbol without its ray_ ("ray_xbar" -> "xbar"); a family whose text is spelled otherwise passes its own ("as").
+ * HAND_NAMES_SYMBOL: the error says "no host ray_med to delegate to" where the others say "no host function".  Every reason but the set verbs' planner
+ * messages is a short literal; those are cut at 300 bytes, as they always were.  (delegate_select, refused1/2/n, cmp_impl, arith_impl, fold_impl and the
+ * joins word their own.) */
+enum { HAND_QUIET = 1, HAND_NAMES_SYMBOL = 2 };
+static obj_p hand_off(int f, const char *label, int flags, int arity, obj_p *x, int64_t n, const char *why) {
+    if (!label) label = VERB[f].host + 4;
+    if (!(flags & HAND_QUIET)) snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", label, why);
+    if (H.bound == 1 && H.f[f]) {
+        if (arity == 1) return HOST_CALL(((rfx_unary_f)H.f[f])(x[0]));
+        if (arity == 2) return HOST_CALL(((rfx_binary_f)H.f[f])(x[0], x[1]));
+        return HOST_CALL(((rfx_vary_f)H.f[f])(x, n));
+    }
+    char b[512];
+    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%.300s) and no host %s to delegate to", label, why, (flags & HAND_NAMES_SYMBOL) ? VERB[f].host : "function");
+    return fail(b);
+}
+/* ... of a unary (y NULL) or binary verb */
+static obj_p hand_off_xy(int f, const char *label, obj_p x, obj_p y, const char *why) {
+    obj_p a[2] = {x, y};
+    return hand_off(f, label, 0, y ? 2 : 1, a, 2, why);
+}
 static obj_p delegate_select(obj_p dict, const char *why) {
     g_last_gpu = 0;
     snprintf(g_err, sizeof(g_err), "rfx_select: handed to the host (%s)", why); /* rfx_ops_last_error(): why the last query was delegated */

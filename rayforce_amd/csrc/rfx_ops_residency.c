@@ -460,9 +460,16 @@ static size_t cache_budget(void) {
     return e ? (size_t)strtoull(e, NULL, 10) : (size_t)200 << 30; /* of the 288 GB of HBM3E */
 }
 
-/* per-call device scratch (temporaries of the operator call in flight): released by op_end() */
-static void *g_optmp[64];
+/* per-call device scratch (temporaries of the operator call in flight), each block on its shard's context: released by op_end() */
+static struct { void *d; int shard; } g_optmp[64];
 static int g_noptmp;
+static int op_scratch_on(int s, void **d, size_t bytes) {
+    if (g_noptmp >= (int)(sizeof(g_optmp) / sizeof(g_optmp[0]))) return RFX_ELIMIT;
+    const int rc = rfx_hip_malloc(g_ctxs[s], d, bytes ? bytes : 8);
+    if (rc == RFX_OK) g_optmp[g_noptmp].d = *d, g_optmp[g_noptmp++].shard = s;
+    return rc;
+}
+static int op_scratch(void **d, size_t bytes) { return op_scratch_on(0, d, bytes); } /* (on shard 0's device, where the operators that are not sharded run) */
 /* ONE lock around everything this file keeps between calls (residency cache, per-operator scratch lists, the device context): the reference
  * calls built-ins from its pool workers, each with its own VM (core/pool.c:168-219), so two rfx_* calls may arrive at once.  An operator
  * holds the lock from op_begin to op_end; a thread that re-enters (the host evaluating `from:` calls an rfx_* built-in) counts depth
@@ -481,7 +488,11 @@ static void op_begin(void) {
     g_stat[ST_OPS]++;
 }
 static void op_scratch_release(void) {
-    for (int i = 0; i < g_noptmp; i++) rfx_hip_free(g_ctx, g_optmp[i]);
+    for (int i = 0; i < g_noptmp; i++) {
+        if (g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctxs[g_optmp[i].shard]);
+        rfx_hip_free(g_ctxs[g_optmp[i].shard], g_optmp[i].d);
+    }
+    if (g_noptmp && g_nshards > 1) rfx_hip_ctx_bind_thread(g_ctx);
     g_noptmp = 0;
 }
 static void op_end(void) {
@@ -510,15 +521,18 @@ static void host_call_end(int d) {
     }
 }
 #define HOST_CALL(call) ({ const int _hd = host_call_begin(); obj_p _hr = (call); host_call_end(_hd); _hr; })
+/* an entry point that is nothing but its implementation between op_begin and op_end: unary (x), binary (x, y), variadic (x, n) */
+#define OP_BODY(call) { op_begin(); obj_p r = (call); op_end(); return r; }
+#define OP1(name, call) rfx_obj_p name(rfx_obj_p x) OP_BODY(call)
+#define OP2(name, call) rfx_obj_p name(rfx_obj_p x, rfx_obj_p y) OP_BODY(call)
+#define OPN(name, call) rfx_obj_p name(rfx_obj_p *x, int64_t n) OP_BODY(call)
 /* device copy of a vector that lives for this call only (never cached) */
 static int transient(obj_p v, const void **dev) {
     const int esz = (v->type == RFX_TYPE_B8) ? 1 : 8;
     const size_t bytes = (size_t)v->len * esz;
-    if (g_noptmp >= (int)(sizeof(g_optmp) / sizeof(g_optmp[0]))) return RFX_ELIMIT;
     void *d = NULL;
-    int rc = rfx_hip_malloc(g_ctx, &d, bytes ? bytes : 8);
+    int rc = op_scratch(&d, bytes);
     if (rc != RFX_OK) return rc;
-    g_optmp[g_noptmp++] = d;
     if (bytes) rc = rfx_hip_h2d_pipelined(g_ctx, d, RFX_AS_RAW(v), bytes);
     g_stat[ST_UPLOADS]++;
     *dev = d;

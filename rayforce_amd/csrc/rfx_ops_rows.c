@@ -1,6 +1,7 @@
 /* rfx_ops_rows.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own).
  * The row verbs as built-ins of their own: filter (ray_filter, core/items.c:338-396), take (ray_take, core/items.c:398-734), reverse (ray_reverse,
- * core/compose.c:144-202) on the device (rfx_rows.hip through rfx_exec_rows.c).  The family's hand-off rule: a shape the device does not take is the
+ * core/compose.c:144-202) on the device (rfx_rows.hip through rfx_exec_rows.c).
+ * The hand-off is the shared one (hand_off, rfx_ops_plan.c): a shape the device does not take is the
  * host's own verb when a host is bound, else an error object naming the reason (also in rfx_ops_last_error()).  Every result is fresh host vectors with
  * the reference's cells, type codes and attributes (a table: a fresh table of them over a clone of the names). */
 static int g_last_rows_gpu = 0;
@@ -8,11 +9,7 @@ int rfx_last_rows_on_gpu(void) { return g_last_rows_gpu; }
 
 static obj_p rows_host(int f, obj_p x, obj_p y, const char *why) {
     g_last_rows_gpu = 0;
-    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
-    if (H.bound == 1 && H.f[f]) return y ? HOST_CALL(((rfx_binary_f)H.f[f])(x, y)) : HOST_CALL(((rfx_unary_f)H.f[f])(x));
-    char b[256];
-    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%s) and no host function to delegate to", HOST_FN[f] + 4, why);
-    return fail(b);
+    return hand_off_xy(f, NULL, x, y, why);
 }
 /* the cell kind of a row type (bytes of a result cell), 0: not a row type */
 static int rows_kind(int type) {
@@ -102,11 +99,9 @@ static obj_p filter_impl(obj_p x, obj_p mask) {
     const void *dm = NULL;
     int rc = mask->mmod == RFX_MMOD_DEVICE ? resident(mask, 0, &dm) : (g_nshards > 1 ? transient_sharded(mask, &dm) : transient(mask, &dm));
     for (int k = 0; k < S.ncols && rc == RFX_OK; k++) {
-        const void *d = NULL;
-        rc = resident(S.cols[k], 0, &d);
+        rc = col_pieces(S.cols[k], (const void **)pieces[k].d);
+        if (rc == COL_PIECE_MISSING) rc = RFX_ELIMIT;
         kinds[k] = rows_kind(S.cols[k]->type);
-        for (int s = 0; s < g_nshards && rc == RFX_OK; s++)
-            if (!(pieces[k].d[s] = shard_piece(d, s))) rc = RFX_ELIMIT;
     }
     rfx_rows_t R;
     memset(&R, 0, sizeof(R));
@@ -192,7 +187,7 @@ static obj_p take_impl(obj_p from, obj_p count) {
         if (g_nshards > 1) return rows_host(F_TAKE, from, count, "take over a sharded table");
         const uint64_t bits = kind == RFX_ROWS_8 ? (uint64_t)from->i64 : (kind == RFX_ROWS_4W ? (uint64_t)(uint32_t)from->i32 : (uint64_t)(uint8_t)from->b8);
         void *d = NULL;
-        int at = ROWS_AT_SCRATCH, rc = sort_tmp(&d, (size_t)m * (size_t)kind);
+        int at = ROWS_AT_SCRATCH, rc = op_scratch(&d, (size_t)m * (size_t)kind);
         if (rc == RFX_OK) at = ROWS_AT_PLANNER, rc = rfx_exec_take_atom(g_x, kind, bits, m, d);
         if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return rows_host(F_TAKE, from, count, rows_limit_why(rc, at, "take over a sharded table"));
         if (rc != RFX_OK) return fail_hip("take");
@@ -295,7 +290,7 @@ static obj_p reverse_impl(obj_p x) {
     const void *dv = NULL;
     void *d = NULL;
     int at = ROWS_AT_UPLOAD, rc = resident(x, 0, &dv);
-    if (rc == RFX_OK) at = ROWS_AT_SCRATCH, rc = sort_tmp(&d, (size_t)l * (size_t)kind);
+    if (rc == RFX_OK) at = ROWS_AT_SCRATCH, rc = op_scratch(&d, (size_t)l * (size_t)kind);
     if (rc == RFX_OK) at = ROWS_AT_PLANNER, rc = rfx_exec_reverse(g_x, dv, kind, l, d);
     if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return rows_host(F_REVERSE, x, NULL, rows_limit_why(rc, at, "reverse over a sharded table"));
     if (rc != RFX_OK && at == ROWS_AT_UPLOAD) return fail_hip("column upload");
@@ -310,21 +305,6 @@ static obj_p reverse_impl(obj_p x) {
     return out;
 }
 
-rfx_obj_p rfx_filter(rfx_obj_p x, rfx_obj_p mask) {
-    op_begin();
-    obj_p r = filter_impl(x, mask);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_take(rfx_obj_p from, rfx_obj_p count) {
-    op_begin();
-    obj_p r = take_impl(from, count);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_reverse(rfx_obj_p x) {
-    op_begin();
-    obj_p r = reverse_impl(x);
-    op_end();
-    return r;
-}
+OP2(rfx_filter, filter_impl(x, y))
+OP2(rfx_take, take_impl(x, y))
+OP1(rfx_reverse, reverse_impl(x))

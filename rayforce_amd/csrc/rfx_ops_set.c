@@ -15,11 +15,7 @@ static obj_p set_host(int f, obj_p x, obj_p y, const char *why) {
     g_last_set_gpu = 0;
     g_last_set_route = RFX_SET_ROUTE_NONE;
     g_set_stat[SST_DELEGATED]++;
-    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
-    if (H.bound == 1 && H.f[f]) return y ? HOST_CALL(((rfx_binary_f)H.f[f])(x, y)) : HOST_CALL(((rfx_unary_f)H.f[f])(x));
-    char b[512];
-    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%.300s) and no host function to delegate to", HOST_FN[f] + 4, why);
-    return fail(b);
+    return hand_off_xy(f, NULL, x, y, why);
 }
 static int set_key_type(obj_p c) { return c->type == RFX_TYPE_I64 || c->type == RFX_TYPE_SYMBOL || c->type == RFX_TYPE_TIMESTAMP; }
 /* the planner's verdict on a call: the host's verb for a shape the reference cannot answer, for scratch that does not fit and for shards */
@@ -64,45 +60,33 @@ static obj_p set_impl(int verb, int f, obj_p x, obj_p y) {
     switch (verb) {
     case SET_DISTINCT:
     case SET_UNION:
-        if (sort_tmp(&dout, (size_t)(nx + ny) * 8) != RFX_OK) return set_host(f, x, binary ? y : NULL, "device memory");
+        if (op_scratch(&dout, (size_t)(nx + ny) * 8) != RFX_OK) return set_host(f, x, binary ? y : NULL, "device memory");
         rc = rfx_exec_distinct(g_x, (const int64_t *)dx, nx, (const int64_t *)dy, ny, (int64_t *)dout, &nout, &route);
         if (rc != RFX_OK) return set_declined(f, x, binary ? y : NULL, rc, route);
         return set_result(x->type, nout, dout, 8, ATTR_DISTINCT_, route);
     case SET_IN:
-        if (sort_tmp(&dout, (size_t)nx) != RFX_OK) return set_host(f, x, y, "device memory");
+        if (op_scratch(&dout, (size_t)nx) != RFX_OK) return set_host(f, x, y, "device memory");
         rc = rfx_exec_member(g_x, (const int64_t *)dx, nx, (const int64_t *)dy, ny, 0, dout, &route);
         if (rc != RFX_OK) return set_declined(f, x, y, rc, route);
         return set_result(RFX_TYPE_B8, nx, dout, 1, 0, route);
     case SET_FIND:
-        if (sort_tmp(&dout, (size_t)ny * 8) != RFX_OK) return set_host(f, x, y, "device memory");
+        if (op_scratch(&dout, (size_t)ny * 8) != RFX_OK) return set_host(f, x, y, "device memory");
         rc = rfx_exec_member(g_x, (const int64_t *)dx, nx, (const int64_t *)dy, ny, 1, dout, &route);
         if (rc != RFX_OK) return set_declined(f, x, y, rc, route);
         return set_result(RFX_TYPE_I64, nx == 0 ? 0 : ny, dout, 8, 0, route); /* (an empty x: I64(0), core/index.c:1512) */
     default:
-        if (sort_tmp(&dout, (size_t)nx * 8) != RFX_OK) return set_host(f, x, y, "device memory");
+        if (op_scratch(&dout, (size_t)nx * 8) != RFX_OK) return set_host(f, x, y, "device memory");
         rc = rfx_exec_set_filter(g_x, (const int64_t *)dx, nx, (const int64_t *)dy, ny, atom, atom ? y->i64 : 0, verb == SET_SECT, (int64_t *)dout, &nout, &route);
         if (rc != RFX_OK) return set_declined(f, x, y, rc, route);
         return set_result(x->type, nout, dout, 8, 0, route);
     }
 }
-rfx_obj_p rfx_distinct(rfx_obj_p x) {
-    op_begin();
-    obj_p r = set_impl(SET_DISTINCT, F_DISTINCT, x, NULL);
-    op_end();
-    return r;
-}
-#define SET_BINARY(name, verb, f)         \
-    rfx_obj_p name(rfx_obj_p x, rfx_obj_p y) { \
-        op_begin();                       \
-        obj_p r = set_impl(verb, f, x, y); \
-        op_end();                         \
-        return r;                         \
-    }
-SET_BINARY(rfx_find, SET_FIND, F_FIND)
-SET_BINARY(rfx_in, SET_IN, F_IN)
-SET_BINARY(rfx_sect, SET_SECT, F_SECT)
-SET_BINARY(rfx_except, SET_EXCEPT, F_EXCEPT)
-SET_BINARY(rfx_union, SET_UNION, F_UNION)
+OP1(rfx_distinct, set_impl(SET_DISTINCT, F_DISTINCT, x, NULL))
+OP2(rfx_find, set_impl(SET_FIND, F_FIND, x, y))
+OP2(rfx_in, set_impl(SET_IN, F_IN, x, y))
+OP2(rfx_sect, set_impl(SET_SECT, F_SECT, x, y))
+OP2(rfx_except, set_impl(SET_EXCEPT, F_EXCEPT, x, y))
+OP2(rfx_union, set_impl(SET_UNION, F_UNION, x, y))
 /* (rfx_set_stats 0): the set verbs' counters since load as an I64 vector -- [calls answered by the device path, calls handed to the host's ray_*
  * (or refused for want of one), then the answered ones by route: nothing to look up, dense, hash, disjoint scopes, except's atom].  What a
  * drop-in test asserts to know that a set verb's answer came from the device (rfx_stats keeps its 17 cells). */

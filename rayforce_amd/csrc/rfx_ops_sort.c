@@ -16,30 +16,14 @@ enum { SORT_IASC, SORT_IDESC, SORT_ASC, SORT_DESC, SORT_RANK };
 static int g_last_sort_gpu = 0;
 int rfx_last_sort_on_gpu(void) { return g_last_sort_gpu; }
 
-static obj_p sort_host(int f, obj_p x, obj_p y, const char *why) {
+static obj_p sort_host(int f, obj_p x, obj_p y, const char *why) { /* (the shared hand_off, rfx_ops_plan.c) */
     g_last_sort_gpu = 0;
-    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
-    if (H.bound == 1 && H.f[f]) return y ? HOST_CALL(((rfx_binary_f)H.f[f])(x, y)) : HOST_CALL(((rfx_unary_f)H.f[f])(x));
-    char b[256];
-    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%s) and no host function to delegate to", HOST_FN[f] + 4, why);
-    return fail(b);
+    return hand_off_xy(f, NULL, x, y, why);
 }
-/* device scratch of this call: released by op_end() with the transients */
-static int sort_tmp(void **d, size_t bytes) {
-    if (g_noptmp >= (int)(sizeof(g_optmp) / sizeof(g_optmp[0]))) return RFX_ELIMIT;
-    int rc = rfx_hip_malloc(g_ctx, d, bytes ? bytes : 8);
-    if (rc == RFX_OK) g_optmp[g_noptmp++] = *d;
-    return rc;
-}
-/* a resident column as the planner's per-shard pieces */
+/* a resident column as the planner's per-shard pieces (a missing piece fails like an upload) */
 static int sort_pieces(obj_p c, rfx_qcol_t *q) {
-    const void *d = NULL;
-    int rc = resident(c, 0, &d);
-    if (rc != RFX_OK) return rc;
     memset(q, 0, sizeof(*q));
-    for (int s = 0; s < g_nshards; s++)
-        if (!(q->d[s] = shard_piece(d, s))) return RFX_ELIMIT;
-    return RFX_OK;
+    return col_pieces(c, (const void **)q->d);
 }
 /* the pieces of a resident column laid end to end at d_whole on shard 0's device (n cells of 8 bytes) */
 static int sort_whole(obj_p c, int64_t n, void *d_whole) {
@@ -61,19 +45,9 @@ static obj_p sort_iota(int64_t n, int down) {
     o->attrs = (uint8_t)((down ? ATTR_DESC_ : ATTR_ASC_) | ATTR_DISTINCT_);
     return o;
 }
-/* bytes of one cell of a vector type the vector verbs take (0: another type) */
-static size_t sort_cell_bytes(int type) {
-    switch (type) {
-        case RFX_TYPE_B8: case RFX_TYPE_U8: return 1;
-        case RFX_TYPE_I16: return 2;
-        case RFX_TYPE_I32: case RFX_TYPE_DATE: case RFX_TYPE_TIME: return 4;
-        case RFX_TYPE_I64: case RFX_TYPE_TIMESTAMP: case RFX_TYPE_F64: return 8;
-        default: return 0;
-    }
-}
 static obj_p sort_reversed(obj_p x) { /* ray_reverse (core/compose.c:144-202): ATTR_ASC and ATTR_DESC change places, the other attributes stay */
     obj_p o = H.vector(x->type, x->len);
-    const size_t w = sort_cell_bytes(x->type);
+    const size_t w = cell_bytes(x->type);
     const char *src = (const char *)RFX_AS_RAW(x);
     char *dst = (char *)RFX_AS_RAW(o);
     for (int64_t i = 0; i < x->len; i++) memcpy(dst + (size_t)i * w, src + (size_t)(x->len - 1 - i) * w, w);
@@ -83,7 +57,7 @@ static obj_p sort_reversed(obj_p x) { /* ray_reverse (core/compose.c:144-202): A
 static obj_p sort_unary(int kind, int f, obj_p x) {
     rfx_host_bind();
     if (!x) return fail("sort: null argument");
-    const size_t w = x->type > 0 ? sort_cell_bytes(x->type) : 0; /* (SYMBOL, C8, LIST ...: 0) */
+    const size_t w = x->type > 0 ? cell_bytes(x->type) : 0; /* (SYMBOL, C8, LIST ...: 0) */
     if (!w) return sort_host(f, x, NULL, "key type");
     const int wide = w == 8, i32 = IS_I32_FAMILY(x->type);
     if (x->mmod == RFX_MMOD_DEVICE && !wide && x->type != RFX_TYPE_B8) return sort_host(f, x, NULL, "a device column that is not I64 / F64 / TIMESTAMP / B8");
@@ -124,11 +98,10 @@ static obj_p sort_unary(int kind, int f, obj_p x) {
     int rc = RFX_OK;
     int32_t type; /* as the planner takes it */
     if (x->type == RFX_TYPE_I16 || x->type == RFX_TYPE_U8) { /* (the residency cache keeps 8-byte, widened 4-byte and B8 columns: raw cells for this call only) */
-        void *raw = NULL;
-        rc = sort_tmp(&raw, (size_t)n * w);
-        if (rc == RFX_OK && rfx_hip_h2d_pipelined(g_ctx, raw, RFX_AS_RAW(x), (size_t)n * w) != RFX_OK) return fail_hip("column upload");
-        if (rc == RFX_OK) g_stat[ST_UPLOADS]++;
-        dv = raw;
+        const void *raw[RFX_MAX_SHARDS]; /* (one shard here: narrow keys over shards went to the host above) */
+        rc = raw_pieces(x, w, raw);
+        if (rc != RFX_OK && raw[0]) return fail_hip("column upload"); /* (a failed copy; scratch that does not fit is the host's verb below) */
+        dv = raw[0];
         type = x->type == RFX_TYPE_I16 ? RFX_I16 : RFX_U8;
     } else {
         if (g_nshards > 1) {
@@ -138,8 +111,8 @@ static obj_p sort_unary(int kind, int f, obj_p x) {
         type = i32 ? (g_nshards > 1 ? RFX_I64 : RFX_I32_WIDE) : x->type == RFX_TYPE_B8 ? RFX_B8 : col_ctype(x);
     }
     const size_t ow = values ? w : 8; /* bytes of one cell of the answer */
-    if (rc == RFX_OK) rc = sort_tmp(&d0, (size_t)n * 8);
-    if (rc == RFX_OK && (kind == SORT_RANK || (values && i32 && g_nshards > 1))) rc = sort_tmp(&d1, (size_t)n * 8);
+    if (rc == RFX_OK) rc = op_scratch(&d0, (size_t)n * 8);
+    if (rc == RFX_OK && (kind == SORT_RANK || (values && i32 && g_nshards > 1))) rc = op_scratch(&d1, (size_t)n * 8);
     const void *d_res = d0;
     if (rc == RFX_OK) {
         const void *cols[1] = {dv};
@@ -204,7 +177,7 @@ static obj_p sort_table(int desc, int f, obj_p t, obj_p y) {
             if ((g_nshards > 1 ? sort_pieces(kc[k], &qk[k]) : resident(kc[k], 0, &dk[k])) != RFX_OK) return fail_hip("column upload");
             types[k] = col_ctype(kc[k]);
         }
-        int rc = sort_tmp(&d, (size_t)n * 8);
+        int rc = op_scratch(&d, (size_t)n * 8);
         if (rc == RFX_OK) rc = g_nshards > 1 ? rfx_exec_sort_shards(g_x, qk, types, nk, desc, n, (int64_t *)d, NULL) : rfx_exec_sort(g_x, dk, types, nk, desc, n, (int64_t *)d);
         if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return sort_host(f, t, y, rc == RFX_ENOMEM ? "device memory" : SORT_LIMIT_WHY);
         if (rc != RFX_OK) return fail_hip("sort");
@@ -260,27 +233,10 @@ static obj_p sort_table(int desc, int f, obj_p t, obj_p y) {
     g_last_sort_gpu = on_gpu;
     return H.table(H.clone(names), rv);
 }
-#define SORT_UNARY(name, kind, f)          \
-    rfx_obj_p name(rfx_obj_p x) {          \
-        op_begin();                        \
-        obj_p r = sort_unary(kind, f, x);  \
-        op_end();                          \
-        return r;                          \
-    }
-SORT_UNARY(rfx_iasc, SORT_IASC, F_IASC)
-SORT_UNARY(rfx_idesc, SORT_IDESC, F_IDESC)
-SORT_UNARY(rfx_asc, SORT_ASC, F_ASC)
-SORT_UNARY(rfx_desc, SORT_DESC, F_DESC)
-SORT_UNARY(rfx_rank, SORT_RANK, F_RANK)
-rfx_obj_p rfx_xasc(rfx_obj_p t, rfx_obj_p y) {
-    op_begin();
-    obj_p r = sort_table(0, F_XASC, t, y);
-    op_end();
-    return r;
-}
-rfx_obj_p rfx_xdesc(rfx_obj_p t, rfx_obj_p y) {
-    op_begin();
-    obj_p r = sort_table(1, F_XDESC, t, y);
-    op_end();
-    return r;
-}
+OP1(rfx_iasc, sort_unary(SORT_IASC, F_IASC, x))
+OP1(rfx_idesc, sort_unary(SORT_IDESC, F_IDESC, x))
+OP1(rfx_asc, sort_unary(SORT_ASC, F_ASC, x))
+OP1(rfx_desc, sort_unary(SORT_DESC, F_DESC, x))
+OP1(rfx_rank, sort_unary(SORT_RANK, F_RANK, x))
+OP2(rfx_xasc, sort_table(0, F_XASC, x, y))
+OP2(rfx_xdesc, sort_table(1, F_XDESC, x, y))

@@ -1,13 +1,6 @@
 /* rfx_ops_verbs.c -- part of the operator layer's ONE translation unit (rfx_ops.c #includes it -- the Makefile does not compile it on its own; the pieces share file-static state and helpers).
  * residency verbs (pin / unpin / invalidate), rfx_stats. */
 /* ------------------------------------------------------------------------------------------------ residency verbs */
-static obj_p pin_impl(obj_p x, int pin);
-static obj_p pin_op(obj_p x, int pin) {
-    op_begin();
-    obj_p r = pin_impl(x, pin);
-    op_end();
-    return r;
-}
 static obj_p pin_impl(obj_p x, int pin) {
     rfx_host_bind();
     if (!x) return fail("pin: null argument");
@@ -49,8 +42,8 @@ static obj_p pin_impl(obj_p x, int pin) {
     }
     return H.clone(x);
 }
-rfx_obj_p rfx_pin(rfx_obj_p x) { return pin_op(x, 1); }
-rfx_obj_p rfx_unpin(rfx_obj_p x) { return pin_op(x, 0); }
+OP1(rfx_pin, pin_impl(x, 1))
+OP1(rfx_unpin, pin_impl(x, 0))
 /* (rfx_invalidate x): the host is about to write (or has just written) into vector x / the columns of table x in place: every
  * cached device copy that overlaps their payload is dropped, pinned or not.  The hook a host patch calls from `set` on a column and
  * from the rc == 1 in-place arithmetic (core/math.c:2248, :2310), see INTEGRATION.md. */

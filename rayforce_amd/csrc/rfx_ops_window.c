@@ -10,14 +10,9 @@ int rfx_last_window_on_gpu(void) { return g_last_window_gpu; }
 #define WJ_MAX_COLS 16
 
 static obj_p window_host(int closed, obj_p *x, int64_t n, const char *why) {
-    const int f = closed ? F_WJ1 : F_WJ;
     g_last_window_gpu = 0;
     g_window_handed = 1;
-    snprintf(g_err, sizeof(g_err), "%s: handed to the host (%s)", HOST_FN[f] + 4, why);
-    if (H.bound == 1 && H.f[f]) return HOST_CALL(((rfx_vary_f)H.f[f])(x, n));
-    char b[256];
-    snprintf(b, sizeof(b), "%s: not covered by the MI355X path (%s) and no host function to delegate to", HOST_FN[f] + 4, why);
-    return fail(b);
+    return hand_off(closed ? F_WJ1 : F_WJ, NULL, 0, 0, x, n, why);
 }
 /* (agg col): the aggregate as RFX_WAGG_*, by function object or by its name; -1: not one of the seven */
 static int window_agg(obj_p head) {
@@ -36,25 +31,12 @@ static obj_p window_impl(int closed, obj_p *x, int64_t n) {
     if (n != 5 || !x || !x[0] || !x[1] || !x[2] || !x[3] || !x[4]) return window_host(closed, x, n, "expected (keys, windows, left table, right table, aggregates)");
     if (x[0]->type != RFX_TYPE_SYMBOL || x[1]->type != RFX_TYPE_LIST || x[2]->type != RFX_TYPE_TABLE || x[3]->type != RFX_TYPE_TABLE || x[4]->type != RFX_TYPE_DICT)
         return window_host(closed, x, n, "expected (symbol vector, list, table, table, dict)");
-    obj_p ksyms = x[0], wins = x[1], lt = x[2], rt = x[3], dict = x[4];
-    if (ksyms->len < 2) return window_host(closed, x, n, "fewer than two key names");
-    if (is_parted_table(lt) || is_parted_table(rt)) return window_host(closed, x, n, "parted table");
+    obj_p ksyms = x[0], wins = x[1], lt = x[2], rt = x[3], dict = x[4], lk[RFX_MAX_KEYS], rk[RFX_MAX_KEYS], ltime = NULL, rtime = NULL;
+    const char *bad = join_key_tuple(ksyms, lt, rt, 1, lk, rk, &ltime, &rtime); /* (rfx_ops_asof.c) */
+    if (bad) return window_host(closed, x, n, bad);
     obj_p lnames = RFX_AS_LIST(lt)[0], lcols = RFX_AS_LIST(lt)[1], rcols = RFX_AS_LIST(rt)[1];
     const int64_t nl = lcols->len ? RFX_AS_LIST(lcols)[0]->len : 0, nr = rcols->len ? RFX_AS_LIST(rcols)[0]->len : 0;
     const int nk = (int)ksyms->len - 1; /* the equality keys; the last name is the window column */
-    if (nk > RFX_MAX_KEYS) return window_host(closed, x, n, "more than 8 equality keys");
-    obj_p ltime = table_col(lt, RFX_AS_I64(ksyms)[nk]), rtime = table_col(rt, RFX_AS_I64(ksyms)[nk]);
-    if (!ltime || !rtime) return window_host(closed, x, n, "window column missing from a table");
-    if (ltime->type != rtime->type) return window_host(closed, x, n, "window columns of different types");
-    /* (an I64 / TIMESTAMP window column is read through AS_I32 by the reference: DESIGN.md, reference defects observed -- whatever it answers, it is the host's) */
-    if (!IS_I32_FAMILY(ltime->type)) return window_host(closed, x, n, "window column type");
-    obj_p lk[RFX_MAX_KEYS], rk[RFX_MAX_KEYS];
-    for (int i = 0; i < nk; i++) {
-        lk[i] = table_col(lt, RFX_AS_I64(ksyms)[i]);
-        rk[i] = table_col(rt, RFX_AS_I64(ksyms)[i]);
-        if (!lk[i] || !rk[i] || lk[i]->type <= 0 || rk[i]->type <= 0 || col_ctype(lk[i]) != RFX_I64 || col_ctype(rk[i]) != RFX_I64 || lk[i]->type != rk[i]->type)
-            return window_host(closed, x, n, "equality key is not an 8-byte integer column of both tables");
-    }
     for (int64_t i = 0; i < lcols->len; i++)
         if (RFX_AS_LIST(lcols)[i]->type <= 0 || RFX_AS_LIST(lcols)[i]->len != nl) return window_host(closed, x, n, "columns of different lengths");
     for (int64_t i = 0; i < rcols->len; i++)
@@ -114,7 +96,7 @@ static obj_p window_impl(int closed, obj_p *x, int64_t n) {
         /* (4-byte columns are resident as their widened copies, rfx_hip_widen_i32: order and nulls survive) */
         if (resident(wlo, 0, &dlo) != RFX_OK || resident(whi, 0, &dhi) != RFX_OK || resident(rtime, 0, &drt) != RFX_OK) { res = fail_hip("column upload"); goto drop; }
         void *perm = NULL, *li = NULL, *ri = NULL;
-        if (sort_tmp(&perm, (size_t)nr * 8) != RFX_OK || sort_tmp(&li, (size_t)nl * 8) != RFX_OK || sort_tmp(&ri, (size_t)nl * 8) != RFX_OK) { why = "device memory"; goto drop; }
+        if (op_scratch(&perm, (size_t)nr * 8) != RFX_OK || op_scratch(&li, (size_t)nl * 8) != RFX_OK || op_scratch(&ri, (size_t)nl * 8) != RFX_OK) { why = "device memory"; goto drop; }
         int collision = 0;
         int64_t stats[2];
         int rc = rfx_exec_window_ranges(g_x, dlk, drk, nk, (const int64_t *)dlo, (const int64_t *)dhi, (const int64_t *)drt, nl, nr, closed, (int64_t *)perm,
@@ -126,7 +108,7 @@ static obj_p window_impl(int closed, obj_p *x, int64_t n) {
             void *outs[RFX_WAGG_N] = {0};
             for (int i = 0; i < nagg; i++)
                 if (aggcol[i] == k) {
-                    if (!dout[agg[i]] && sort_tmp(&dout[agg[i]], (size_t)nl * 8) != RFX_OK) { why = "device memory"; goto drop; }
+                    if (!dout[agg[i]] && op_scratch(&dout[agg[i]], (size_t)nl * 8) != RFX_OK) { why = "device memory"; goto drop; }
                     outs[agg[i]] = dout[agg[i]];
                 }
             if (resident(vcol[k], 0, &dv) != RFX_OK) { res = fail_hip("column upload"); goto drop; }
