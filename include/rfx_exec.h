@@ -355,6 +355,14 @@ int rfx_exec_reverse(rfx_exec_t *x, const void *d_col, int32_t kind, int64_t l, 
  *   enqueued on its context.  RFX_EINVAL: the reference has no such arm (rfx_hip_cast_arm); RFX_ELIMIT: several ranks.  RFX_XSTAT_CASTS counts. */
 int rfx_exec_cast(rfx_exec_t *x, int32_t src_type, int32_t dst_type, const void *const *d_ins, int64_t n, void *const *d_outs, int shard);
 
+/* ---- concat, raze (rfx_concat.hip) ----
+ * rfx_exec_concat: the spans' cells end to end into d_out (rfx_hip_concat: one launch for any number of spans); kind = the bytes of a cell, 1, 2, 4 or 8.
+ * rfx_exec_concat_cols: the table form -- every column its own spans, width and output, RFX_MAX_COLS columns per launch, more in further launches.
+ * Both read across whole columns and run on one shard, one rank: several answer RFX_ELIMIT, "concat over a sharded column".  Enqueued on shard 0's
+ * context.  RFX_XSTAT_CONCATS counts the calls (a table once), RFX_XSTAT_CONCAT_SPANS the spans given, RFX_XSTAT_CONCAT_CELLS the cells answered. */
+int rfx_exec_concat(rfx_exec_t *x, const rfx_span_t *spans, int64_t nspans, int32_t kind, void *d_out);
+int rfx_exec_concat_cols(rfx_exec_t *x, const rfx_concat_col_t *cols, int ncols);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -404,7 +412,10 @@ enum {
     RFX_XSTAT_SORT_MERGES = 38,   /* sorts over shards answered by local sorts + one multiway merge (rfx_exec_sort_shards) */
     RFX_XSTAT_NS_SORT_LOCAL = 39, /* ... wall time of their local-sort phases (to every shard's stream idle), nanoseconds */
     RFX_XSTAT_NS_SORT_MERGE = 40, /* ... and of the cross-device copies, the merge and the clean-up */
-    RFX_XSTAT_N = 41
+    RFX_XSTAT_CONCATS = 41,       /* concat / raze calls answered by the device path (a table counts once) */
+    RFX_XSTAT_CONCAT_SPANS = 42,  /* ... spans they were given, over all columns (empty ones and atoms included) */
+    RFX_XSTAT_CONCAT_CELLS = 43,  /* ... and cells they answered, over all columns */
+    RFX_XSTAT_N = 44
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

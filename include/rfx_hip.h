@@ -863,6 +863,28 @@ enum { RFX_CAST_B8 = 1, RFX_CAST_U8 = 2, RFX_CAST_I16 = 3, RFX_CAST_I32 = 4, RFX
 int rfx_hip_cast(rfx_ctx_t *ctx, int32_t src_type, int32_t dst_type, const void *d_src, int64_t n, void *d_dst);
 int rfx_hip_cast_arm(int32_t src_type, int32_t dst_type);
 
+/* ---- concat, raze (rfx_concat.hip): spans of cells laid end to end ----
+ * A span is `cells` cells of the column's width at the device address d_ptr (cell-aligned, nothing more), or -- d_ptr NULL, cells 1 -- an atom: the cell in
+ *   the low bytes of `bits`.  Empty spans (cells 0, any address) take no room.
+ * rfx_hip_concat: the spans' cells, in order, into d_out (16-byte aligned, a buffer of its own holding the sum of the cells) in ONE launch for any
+ *   number of spans: the span table (prefix sums and addresses) is uploaded for the call, a workgroup finds its tile's spans by binary search, the
+ *   output moves as whole aligned 16-byte accesses whatever the alignment of a span's source or of its place in the output; nothing is read outside a
+ *   span or written outside the output.  width: 1, 2, 4 or 8 bytes.
+ * rfx_hip_concat_cols: the same for 1 .. RFX_MAX_COLS columns, each with its own spans, width and output, in one launch. */
+typedef struct {
+    const void *d_ptr;
+    int64_t cells;
+    uint64_t bits;
+} rfx_span_t;
+typedef struct {
+    const rfx_span_t *spans;
+    int64_t nspans;
+    int32_t width;
+    void *d_out;
+} rfx_concat_col_t;
+int rfx_hip_concat(rfx_ctx_t *ctx, const rfx_span_t *spans, int64_t nspans, int32_t width, void *d_out);
+int rfx_hip_concat_cols(rfx_ctx_t *ctx, const rfx_concat_col_t *cols, int ncols);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -44,6 +44,8 @@
  *   rfx_find               ray_find              core/items.c:302                binary_f  (x, y) -> I64, the first row of x holding y[j], or null
  *   rfx_sect rfx_except    ray_sect ray_except   core/items.c:898-1019           binary_f  (x, y) I64 or SYMBOL pairs -> the cells of x in / not in y, in x's order
  *   rfx_union              ray_union             core/items.c:1022               binary_f  (x, y) -> distinct of x followed by y, ATTR_DISTINCT
+ *   rfx_concat             ray_concat            core/compose.c:465-823          binary_f  (x, y) vectors of one type, a vector and an atom, two tables -> x's cells, then y's
+ *   rfx_raze               ray_raze              core/compose.c:1096-1164        unary_f   LIST of vectors of one type -> their cells end to end
  *
  * Everything below runs on the MI355X through the flat ABI of rfx_hip.h.  There is NO CPU implementation behind these
  * entry points: queries whose shape the GPU path does not cover are handed back to the host's own ray_* function when
@@ -272,6 +274,27 @@ int rfx_last_rows_on_gpu(void);
 rfx_obj_p rfx_as(rfx_obj_p type_name, rfx_obj_p x);
 /* 1: the last rfx_as was answered by the device path (a clone and an empty vector included: no launch); 0: it went to the host or failed */
 int rfx_last_cast_on_gpu(void);
+
+/* The write side as built-ins of their own (rfx_concat.hip): a table grows by (concat t batch), per-partition answers are put back together by (raze (list
+ * v1 v2 ...)).  "A concat type" below: B8 / U8 / I16 / I32 / DATE / TIME / I64 / SYMBOL / TIMESTAMP / F64.
+ *   binary_f (concat x y)  ray_concat  core/compose.c:465-823    two vectors of one concat type; such a vector and an atom of its type, on either side; two
+ *       TABLEs whose every column is such a vector and whose names are the same set: y's columns are taken in x's name order, the result carries x's names.
+ *   unary_f  (raze l)      ray_raze    core/compose.c:1096-1164  a LIST of one or more vectors that all have one concat type, empties among them included.
+ * Operands are host vectors or I64 / F64 / SYMBOL / TIMESTAMP / B8 device-column handles; every result is fresh host vectors of the operands' type, attribute
+ * byte 0, each column ONE multi-span copy on the device (a table's columns RFX_MAX_COLS to a launch) read back.
+ * THE RESULT INHERITS RESIDENCY: the device buffer of every I64 / SYMBOL / TIMESTAMP / F64 / B8 result column stays in the residency cache as the copy of
+ * the fresh result vector (the cache holds its reference, counts the bytes against its budget and evicts it like any entry), so that an operator over the
+ * answer uploads nothing.  I32 / DATE / TIME results are not adopted (the cache keeps their widened image), I16 / U8 are never resident.
+ * RFX_CONCAT_ADOPT=0 in the environment turns adoption off.
+ * The host's own verb answers everything else -- an atom with an atom; operands of different types (the reference answers a LIST); C8 / GUID / ENUM / LIST /
+ * DICT / MAPLIST operands and parted columns; tables whose name sets differ or whose paired columns differ in type (the reference words those errors
+ * itself); raze of something that is not a list, of an empty list, of elements that are not all vectors of one type; 4-byte, 2-byte and U8 device-column
+ * handles; more than one shard or rank; a result the device has no room for.  Without a host those are refused with the reason, which is also in
+ * rfx_ops_last_error(). */
+rfx_obj_p rfx_concat(rfx_obj_p x, rfx_obj_p y);
+rfx_obj_p rfx_raze(rfx_obj_p list);
+/* 1: the last of those two calls was answered by the device path (an empty result included: no launch); 0: it went to the host or failed */
+int rfx_last_concat_on_gpu(void);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

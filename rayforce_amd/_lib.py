@@ -140,6 +140,7 @@ RFX_Q_ROWS_DIRECT, RFX_Q_ROWS_RING = 64, 128
 RFX_XSTAT_CASTS = 36
 RFX_XSTAT_SCOPE_SPARSE_SAMPLED = 37
 RFX_XSTAT_SORT_MERGES, RFX_XSTAT_NS_SORT_LOCAL, RFX_XSTAT_NS_SORT_MERGE = 38, 39, 40
+RFX_XSTAT_CONCATS, RFX_XSTAT_CONCAT_SPANS, RFX_XSTAT_CONCAT_CELLS = 41, 42, 43
 RFX_MERGE_MAX_RUNS = 16
 # include/rfx_hip.h RFX_CAST_*: the reference's vector type codes rfx_hip_cast / rfx_exec_cast take
 RFX_CAST = {"b8": 1, "u8": 2, "i16": 3, "i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}
@@ -154,6 +155,14 @@ RFX_XSTAT_PHASES = (("scope", 9), ("pass", 10), ("merge", 11), ("rank", 12), ("e
 
 class MergeRun(C.Structure):  # rfx_merge_run_t
     _fields_ = [("d_keys", C.c_void_p * RFX_MAX_KEYS), ("d_rows", C.c_void_p), ("len", C.c_int64), ("row0", C.c_int64)]
+
+
+class Span(C.Structure):  # rfx_span_t
+    _fields_ = [("d_ptr", C.c_void_p), ("cells", C.c_int64), ("bits", C.c_uint64)]
+
+
+class ConcatCol(C.Structure):  # rfx_concat_col_t
+    _fields_ = [("spans", C.POINTER(Span)), ("nspans", C.c_int64), ("width", C.c_int32), ("d_out", C.c_void_p)]
 
 
 class QCol(C.Structure):
@@ -333,6 +342,8 @@ PROTOTYPES = {
     "rfx_hip_rows_fill": (C.c_int, [_ctx, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
     "rfx_hip_cast": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_cast_arm": (C.c_int, [C.c_int32, C.c_int32]),
+    "rfx_hip_concat": (C.c_int, [_ctx, _P(Span), C.c_int64, C.c_int32, C.c_void_p]),
+    "rfx_hip_concat_cols": (C.c_int, [_ctx, _P(ConcatCol), C.c_int]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_set_scope": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_int64)]),
@@ -422,6 +433,8 @@ EXEC_PROTOTYPES = {
     "rfx_exec_take_atom": (C.c_int, [_exec, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p]),
     "rfx_exec_reverse": (C.c_int, [_exec, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "rfx_exec_cast": (C.c_int, [_exec, C.c_int32, C.c_int32, _P(C.c_void_p), C.c_int64, _P(C.c_void_p), C.c_int]),
+    "rfx_exec_concat": (C.c_int, [_exec, _P(Span), C.c_int64, C.c_int32, C.c_void_p]),
+    "rfx_exec_concat_cols": (C.c_int, [_exec, _P(ConcatCol), C.c_int]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_bin": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,

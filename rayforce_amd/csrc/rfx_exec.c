@@ -94,3 +94,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_bucket.c"
 #include "rfx_exec_rows.c"
 #include "rfx_exec_cast.c"
+#include "rfx_exec_concat.c"

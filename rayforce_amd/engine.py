@@ -685,6 +685,58 @@ class Engine:
             self._xcheck(self.lib.rfx_exec_reverse(self._x, t.data_ptr(), kind, t.numel(), out.data_ptr()), "reverse")
         return out
 
+    # ------------------------------------------------------------------ concat, raze (rfx_concat.hip through rfx_exec_concat.c)
+    _CONCAT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64, torch.float64)
+
+    def _concat_cols(self, columns):
+        """columns: per result column a list of parts (device tensors of one dtype, or Python numbers: atoms) -> one fresh tensor per column, every column
+        ONE multi-span copy, RFX_MAX_COLS columns to a launch (rfx_exec_concat_cols).  One shard."""
+        import struct
+        descs = (L.ConcatCol * len(columns))()
+        outs, keep = [], []
+        for k, parts in enumerate(columns):
+            tens = [p.view(torch.int8) if isinstance(p, torch.Tensor) and p.dtype == torch.bool else p for p in parts]
+            dts = {p.dtype for p in tens if isinstance(p, torch.Tensor)}
+            if len(dts) != 1 or next(iter(dts)) not in self._CONCAT_DTYPES:
+                raise RfxError("concat / raze: the parts of a column are tensors of one dtype among int8 (bool), uint8, int16, int32, int64, float64")
+            dt = next(iter(dts))
+            spans = (L.Span * len(tens))()
+            total = 0
+            for i, p in enumerate(tens):
+                if isinstance(p, torch.Tensor):
+                    self._check_col(p)  # (a view t[j:] is contiguous: its cells are cell-aligned, which is all the kernel asks)
+                    spans[i].d_ptr, spans[i].cells = (p.data_ptr() if p.numel() else None), p.numel()
+                else:
+                    fmt = {torch.int64: "<q", torch.float64: "<d", torch.int32: "<i", torch.int16: "<h", torch.int8: "<b", torch.uint8: "<B"}[dt]
+                    spans[i].d_ptr, spans[i].cells = None, 1
+                    spans[i].bits = int.from_bytes(struct.pack(fmt, float(p) if dt == torch.float64 else int(p)), "little")
+                total += spans[i].cells
+            out = self.empty(total, dt)
+            descs[k].spans, descs[k].nspans, descs[k].width, descs[k].d_out = spans, len(tens), out.element_size(), (out.data_ptr() if total else None)
+            outs.append(out)
+            keep.append(spans)
+        if any(o.numel() for o in outs):
+            self._xcheck(self.lib.rfx_exec_concat_cols(self._x, descs, len(columns)), "concat")
+        return outs
+
+    def concat(self, a, b):
+        """(concat a b): two device columns of one dtype, a column and a Python number (an atom of the column's type, on either side), or two dicts of
+        columns with the same names as tables -- b's columns are taken in a's name order, the result carries a's names.  -> fresh tensors."""
+        if isinstance(a, dict) or isinstance(b, dict):
+            if not (isinstance(a, dict) and isinstance(b, dict)) or not a or set(a) != set(b):
+                raise RfxError("concat: tables whose name sets differ")  # reference: err_value
+            return dict(zip(a.keys(), self._concat_cols([[a[n], b[n]] for n in a])))
+        if not isinstance(a, torch.Tensor) and not isinstance(b, torch.Tensor):
+            raise RfxError("concat: an atom with an atom")
+        return self._concat_cols([[a, b]])[0]
+
+    def raze(self, parts):
+        """(raze (list v1 v2 ...)): one or more device columns of one dtype, empties among them included, end to end.  -> a fresh tensor."""
+        parts = list(parts)
+        if not parts or not all(isinstance(p, torch.Tensor) for p in parts):
+            raise RfxError("raze: a non-empty list of device columns")
+        return self._concat_cols([parts])[0]
+
     def eval_expr(self, expr, table=None) -> torch.Tensor:
         """``(op x y)`` / an expression tree over columns and atoms as a device column: ray_add .. ray_mod (binop_map,
         core/math.c:2280-2345) in ONE pass whatever the depth."""

@@ -63,6 +63,9 @@ OPS_PROTOTYPES = {
     "rfx_last_rows_on_gpu": (C.c_int, []),
     "rfx_as": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_last_cast_on_gpu": (C.c_int, []),
+    "rfx_concat": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "rfx_raze": (C.c_void_p, [C.c_void_p]),
+    "rfx_last_concat_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),
