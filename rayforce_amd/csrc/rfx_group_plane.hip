@@ -661,6 +661,14 @@ static size_t plane_agg_lds(const Plan &P, int a0, int a1, i64 local) {
     return (size_t)local * (cells8 * 8 + cells4 * 4) + 16 * 64 * 4 + 64; // tables + the waves' count windows
 }
 #define PL_AGG_LDS_MAX (150 * 1024)
+// rows per row block.  RFX_PLANE_BLOCK_ROWS=<n> (tests): a multiple of 512 in [512, 2^18] -- a few million rows then have the thousands of blocks of a
+// 1e9-row table (the aggregate's region walk, its count windows, first rows as block * block_rows + delta); anything else leaves 2^18.  The kernels
+// take the block size as an argument already.
+static i64 plane_block_rows() {
+    static const char *env = getenv("RFX_PLANE_BLOCK_ROWS");
+    const long n = env ? atol(env) : 0;
+    return (n >= 512 && n <= PL_BLOCK_ROWS && n % 512 == 0) ? (i64)n : (i64)PL_BLOCK_ROWS;
+}
 // can every aggregate be served by SOME pass?  (each alone must fit; passes then take as many as fit)
 static bool plane_agg_fits(const Plan &P, i64 local) {
     for (int a = 0; a < P.nagg; a++)
@@ -674,6 +682,7 @@ struct PlaneState { // what rfx_plane_scope leaves for rfx_plane_accumulate (liv
     const void *key;
     const void *val[PL_MAX_NV];
     i64 nrows;
+    i64 block_rows; // rows per row block of these planes
     i64 seen; // records in the planes (the selected rows)
     u64 sig[RFX_MAX_PREDS][6];
 };
@@ -724,10 +733,11 @@ int rfx_plane_scope(rfx_ctx *c, const Plan &P, int key_idx, const void *d_key, i
     const i64 est_local = (i64)((est_range + (1ULL << pbits) - 1) >> pbits);
     if (est_local > (1 << PL_SLOT_BITS) || !plane_agg_fits(P, est_local)) return RFX_ESTATE;
     const i64 nrows = P.nrows;
-    const i64 nblk64 = (nrows + PL_BLOCK_ROWS - 1) / PL_BLOCK_ROWS;
+    const i64 block_rows = plane_block_rows();
+    const i64 nblk64 = (nrows + block_rows - 1) / block_rows;
     if (nblk64 > (1 << 20) || nrows >= 0xFFFFFFF0LL) return RFX_ESTATE;
     // region size: the expected share of a partition plus room for its spread (uniform keys: sigma = sqrt(share)), whole groups
-    double share = (double)PL_BLOCK_ROWS / (double)(1 << pbits);
+    double share = (double)block_rows / (double)(1 << pbits);
     if (npred > 0) share *= (frac * 1.3 + 0.01 < 1.0 ? frac * 1.3 + 0.01 : 1.0);
     unsigned c0 = (unsigned)(share * 1.25 + 160.0);
     c0 = (c0 + 127u) & ~127u;
@@ -737,7 +747,7 @@ int rfx_plane_scope(rfx_ctx *c, const Plan &P, int key_idx, const void *d_key, i
     plane_layout(c, (int)nblk64, pbits, c0, nv, &A, &need);
     if (rfx_chunk_reserve(c, need) != RFX_OK) return RFX_ESTATE;
     plane_layout(c, (int)nblk64, pbits, c0, nv, &A, NULL);
-    A.block_rows = PL_BLOCK_ROWS;
+    A.block_rows = block_rows;
     // key -> column 0, value plane j -> column 1 + j (the kernel reads them without a run-time select; a value column that IS the key
     // column is listed a second time), the predicates' other columns behind them
     Plan Pc = P;
@@ -793,6 +803,7 @@ int rfx_plane_scope(rfx_ctx *c, const Plan &P, int key_idx, const void *d_key, i
     st->key = d_key;
     for (int j = 0; j < nv; j++) st->val[j] = (const void *)P.cols[vcol[j]];
     st->nrows = nrows;
+    st->block_rows = block_rows;
     st->npred = npred;
     st->logic = logic;
     st->nblk = (int)nblk64;
@@ -861,7 +872,7 @@ int rfx_plane_accumulate(rfx_ctx *c, const Plan &P, int key_idx, const rfx_group
         }
         G.nblk = st->nblk;
         G.pbits = st->pbits;
-        G.block_rows = PL_BLOCK_ROWS;
+        G.block_rows = st->block_rows;
         G.c0 = st->c0;
         G.meta = A.meta;
         G.cnt = A.cnt;
@@ -1359,7 +1370,8 @@ int rfx_plane_hash_accumulate(rfx_ctx *c, const Plan &P, int key_idx, const Hash
         if (est * HEAD / (double)((1 << pbits) << hbits) > (double)lcap) return RFX_ESTATE; // more keys than 512 LDS tables hold: round 1's kernels / the device-wide table
         parts = 1 << pbits;
     }
-    const i64 nblk64 = (nrows + PL_BLOCK_ROWS - 1) / PL_BLOCK_ROWS;
+    const i64 block_rows = plane_block_rows();
+    const i64 nblk64 = (nrows + block_rows - 1) / block_rows;
     if (nblk64 > (1 << 20)) return RFX_ESTATE;
     // key -> columns 0 and 1 (plane 0 IS the key), the value column -> 2 (plane 1; without one, the key again), the predicates' columns behind
     Plan Pc = P;
@@ -1385,7 +1397,7 @@ int rfx_plane_hash_accumulate(rfx_ctx *c, const Plan &P, int key_idx, const Hash
         }
     }
     // selectivity: unknown here -- regions sized for every row (a selective filter only leaves them emptier)
-    double share = (double)PL_BLOCK_ROWS / (double)parts;
+    double share = (double)block_rows / (double)parts;
     unsigned c0 = (unsigned)(share * 1.25 + 160.0);
     c0 = (c0 + 127u) & ~127u;
     PlaneArgs A;
@@ -1394,7 +1406,7 @@ int rfx_plane_hash_accumulate(rfx_ctx *c, const Plan &P, int key_idx, const Hash
     plane_layout(c, (int)nblk64, pbits, c0, 2, &A, &need, parts);
     if (rfx_chunk_reserve(c, need) != RFX_OK) return RFX_ESTATE;
     plane_layout(c, (int)nblk64, pbits, c0, 2, &A, NULL, parts);
-    A.block_rows = PL_BLOCK_ROWS;
+    A.block_rows = block_rows;
     for (int i = 0; i < Pc.npred; i++) {
         A.pmask |= 1u << Pc.preds[i].col;
         if (Pc.preds[i].rhs_col >= 0) A.pmask |= 1u << Pc.preds[i].rhs_col;
@@ -1424,7 +1436,7 @@ int rfx_plane_hash_accumulate(rfx_ctx *c, const Plan &P, int key_idx, const Hash
     X.pbits = pbits;
     X.hbits = hbits;
     X.parts = parts;
-    X.block_rows = PL_BLOCK_ROWS;
+    X.block_rows = block_rows;
     X.c0 = c0;
     X.lcap = lcap;
     X.narr = narr;
