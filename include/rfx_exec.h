@@ -363,6 +363,34 @@ int rfx_exec_cast(rfx_exec_t *x, int32_t src_type, int32_t dst_type, const void 
 int rfx_exec_concat(rfx_exec_t *x, const rfx_span_t *spans, int64_t nspans, int32_t kind, void *d_out);
 int rfx_exec_concat_cols(rfx_exec_t *x, const rfx_concat_col_t *cols, int ncols);
 
+/* ---- upsert, insert (rfx_upsert.hip; ray_upsert / ray_insert, core/update.c:556-750) ----
+ * A batch of m rows against a table of n rows whose first nkeys columns are the key.  Three steps, each enqueued on shard 0's context:
+ * rfx_exec_upsert_index: d_idx[j] = the first table row whose key tuple equals batch row j's, or the null (index_upsert_obj, core/index.c:3001-3065).  One
+ *   key: the set verbs' `find` (rfx_exec_member, its routes and guards: RFX_ESTATE with *undefined = 1 where the reference's own indexing would leave its
+ *   table).  2 .. RFX_MAX_KEYS keys: rfx_exec_join_index (RFX_ESTATE with *undefined = 2: two tuples share one row hash).  n == 0: all nulls, no lookup.
+ *   Key cells are 8-byte integers (I64 / SYMBOL / TIMESTAMP).
+ * rfx_exec_upsert_plan: rfx_hip_upsert_plan -- d_dest[j] and *appended = a.
+ * rfx_exec_upsert_cols: every column's result of n + a cells: the table's n cells by the multi-span copy (rfx_exec_concat_cols), then -- on the same
+ *   stream -- the column's null over the appended cells of an ABSENT column, and the batch cells placed by d_dest, RFX_MAX_COLS columns per launch: a KEY
+ *   column takes appended rows only, a VALUE column matched rows too.  d_out 16-byte aligned, d_batch 16-byte aligned.
+ * rfx_exec_insert_cols: the same with every batch row appended in order: no index, no plan (roles VALUE and ABSENT only).
+ * Scratch is freed before return (RFX_ENOMEM when it does not fit).  One shard, one rank: several answer RFX_ELIMIT, "upsert over a sharded table".
+ * RFX_XSTAT_UPSERTS / _UPSERT_MATCHED / _UPSERT_APPENDED / _INSERTS count; RFX_XSTAT_NS_UPSERT_INDEX / _PLAN / _PLACE: wall time to the stream idle. */
+enum { RFX_UPSERT_KEY = 0, RFX_UPSERT_VALUE = 1, RFX_UPSERT_ABSENT = 2 };
+typedef struct {
+    const void *d_table; /* n cells (NULL when n == 0) */
+    const void *d_batch; /* m cells; NULL: RFX_UPSERT_ABSENT */
+    void *d_out;         /* n + a cells */
+    int32_t width;       /* bytes of a cell: 1, 2, 4 or 8 */
+    int32_t role;        /* RFX_UPSERT_* */
+    uint64_t null_bits;  /* the column's null in the low bytes (ABSENT) */
+} rfx_upsert_xcol_t;
+int rfx_exec_upsert_index(rfx_exec_t *x, const void *const *d_table_keys, const void *const *d_batch_keys, int nkeys, int64_t n, int64_t m, int64_t *d_idx,
+                          int *undefined);
+int rfx_exec_upsert_plan(rfx_exec_t *x, const int64_t *d_idx, int64_t m, int64_t n, int64_t *d_dest, int64_t *appended);
+int rfx_exec_upsert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, const int64_t *d_dest, int64_t m, int64_t n, int64_t appended);
+int rfx_exec_insert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, int64_t m, int64_t n);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -415,7 +443,14 @@ enum {
     RFX_XSTAT_CONCATS = 41,       /* concat / raze calls answered by the device path (a table counts once) */
     RFX_XSTAT_CONCAT_SPANS = 42,  /* ... spans they were given, over all columns (empty ones and atoms included) */
     RFX_XSTAT_CONCAT_CELLS = 43,  /* ... and cells they answered, over all columns */
-    RFX_XSTAT_N = 44
+    RFX_XSTAT_UPSERTS = 44,         /* upsert calls answered by the device path */
+    RFX_XSTAT_UPSERT_MATCHED = 45,  /* ... batch rows that matched a table row (the ones a later row overwrote included) */
+    RFX_XSTAT_UPSERT_APPENDED = 46, /* ... and batch rows appended */
+    RFX_XSTAT_INSERTS = 47,         /* insert calls answered by the device path */
+    RFX_XSTAT_NS_UPSERT_INDEX = 48, /* wall time of the upserts' index step, nanoseconds, to the stream idle */
+    RFX_XSTAT_NS_UPSERT_PLAN = 49,  /* ... of their plan step */
+    RFX_XSTAT_NS_UPSERT_PLACE = 50, /* ... and of the copy, fill and place */
+    RFX_XSTAT_N = 51
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

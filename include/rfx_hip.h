@@ -885,6 +885,30 @@ typedef struct {
 int rfx_hip_concat(rfx_ctx_t *ctx, const rfx_span_t *spans, int64_t nspans, int32_t width, void *d_out);
 int rfx_hip_concat_cols(rfx_ctx_t *ctx, const rfx_concat_col_t *cols, int ncols);
 
+/* ---- upsert, insert (rfx_upsert.hip): a keyed batch of m rows merged into a table of n ----
+ * d_idx[j] is the table row batch row j matched (0 <= row < n) or anything else -- the null, a negative, a row >= n -- for "none".
+ * rfx_hip_upsert_plan: d_dest[j] = that row when j is the LAST batch row that matched it, -1 when a later one did, n + (the number of unmatched rows
+ *   before j) when j matched none; *appended = the unmatched rows.  Last writer wins without clearing n cells: an uninitialised scratch W of n 4-byte
+ *   cells from the context's pool is touched at matched rows only -- store -1, atomicMax(j), compare -- and the unmatched rows are ranked by the ordered
+ *   scan (ballot per wavefront, prefix across waves and blocks).  Four launches on the context's stream, one 8-byte read-back, the scratch (4 B per
+ *   table row + 8 B per 2048 batch rows) freed before return.  m < 2^31 (RFX_ELIMIT), n + m < 2^62.  d_idx, d_dest: 8-byte aligned, m cells.
+ * rfx_hip_upsert_place: for every batch row j with 0 <= d_dest[j] < total and every column k: d_out_k[d_dest[j]] = d_batch_k[j] -- columns with
+ *   appends_only set take the rows with d_dest[j] >= n only (key columns; value columns whose matched rows stay).  1 .. RFX_MAX_COLS columns per launch,
+ *   cells of 1, 2, 4 or 8 bytes; d_dest and every batch column (16-byte aligned, m cells) are read once, 16 bytes per lane; no atomics.  d_dest holds
+ *   every destination at most once (what the plan leaves), so the order of the stores does not matter.  d_dest NULL: d_dest[j] = n + j, every row
+ *   appended in order (insert; total = n + m).
+ * rfx_hip_upsert_fill: `cells` cells of `width` bytes at d_dst (cell-aligned, nothing more) = the low bytes of `bits`: 16-byte stores between a head and
+ *   a tail written byte by byte.  The appended cells of a column the batch does not provide. */
+typedef struct {
+    const void *d_batch;
+    void *d_out;
+    int32_t width;
+    int32_t appends_only;
+} rfx_upsert_col_t;
+int rfx_hip_upsert_plan(rfx_ctx_t *ctx, const int64_t *d_idx, int64_t m, int64_t n, int64_t *d_dest, int64_t *appended);
+int rfx_hip_upsert_place(rfx_ctx_t *ctx, const rfx_upsert_col_t *cols, int ncols, const int64_t *d_dest, int64_t m, int64_t n, int64_t total);
+int rfx_hip_upsert_fill(rfx_ctx_t *ctx, void *d_dst, int32_t width, uint64_t bits, int64_t cells);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

@@ -296,6 +296,30 @@ rfx_obj_p rfx_raze(rfx_obj_p list);
 /* 1: the last of those two calls was answered by the device path (an empty result included: no launch); 0: it went to the host or failed */
 int rfx_last_concat_on_gpu(void);
 
+/* The keyed write (rfx_upsert.hip): a batch merged into a table VALUE; the result is a new table, to be bound by the caller: (set t (upsert t 1 batch)).
+ *   vary_f (upsert t keys batch)  ray_upsert  core/update.c:556-750  keys an -I64 atom, 1 .. 8: the first `keys` columns of t are the key.  Every batch row
+ *       whose key tuple equals a row of t -- the FIRST such row of t as it was -- overwrites that row's value columns, the last such batch row winning;
+ *       every other batch row is appended, in batch order, two rows with the same new key both.
+ *   vary_f (insert t batch)       ray_insert  core/update.c:414-542  every batch row appended.
+ * t: a TABLE whose every column is a plain vector of a concat type, its key columns I64 / SYMBOL / TIMESTAMP.  batch: a LIST of l <= p vectors of the
+ * columns' own types and one length >= 1 (upsert: columns l .. p - 1 keep their matched rows and append their null; insert: l == p), a LIST of atoms (one
+ * record), or a DICT with symbol keys / a TABLE in any name order (a column it misses is a null VECTOR: matched rows take the null too).  Operands are host
+ * vectors or the device-column handles concat takes.  The result: a fresh table over a clone of t's names, every column a fresh host vector of its type,
+ * attribute byte 0; its I64 / SYMBOL / TIMESTAMP / F64 / B8 columns stay resident exactly as concat's do (RFX_CONCAT_ADOPT=0 turns that off).
+ * Handed to the host's own verb (without a host: refused, the reason in rfx_ops_last_error()): the quoted-symbol in-place form; keys > 8 and key columns
+ * of other types; a null or a negative key on find's hash route, a key range beyond 64 bits, two key tuples under one row hash; an F64 batch cell for an
+ * integer column and every other batch type that is not the column's; LIST / ENUM / MAPLIST / C8 / GUID columns and parted tables; DATE / TIME columns, U8
+ * columns under upsert or one record, and a matched row for a B8 / I16 / I32 value column (the reference's set_idx turns those into LIST columns: known
+ * once the index is); a column not provided
+ * whose null(type) is no cell (U8 / I16 / I32 / DATE / TIME under a short LIST or a one-record DICT: the reference answers a LIST column); one record under
+ * two or more keys (the reference does not find its row); a batch of no rows (insert: the reference's length error; upsert: it answers t's own vectors); insert's short LIST (a ragged table); 2^31 or more batch rows; more
+ * than one shard or rank; a result the device has no room for; and every error the reference words itself -- arity, keys < 1, more batch columns than t
+ * has, unequal lengths, unknown DICT names. */
+rfx_obj_p rfx_upsert(rfx_obj_p *x, int64_t n);
+rfx_obj_p rfx_insert(rfx_obj_p *x, int64_t n);
+/* 1: the last of those two calls was answered by the device path; 0: it went to the host or failed */
+int rfx_last_upsert_on_gpu(void);
+
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns
  * carry the mapping's values at the selected rows (value i at row ids[i]; under by: every group's aggregate at all of its selected

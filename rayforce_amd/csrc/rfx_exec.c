@@ -95,3 +95,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_rows.c"
 #include "rfx_exec_cast.c"
 #include "rfx_exec_concat.c"
+#include "rfx_exec_upsert.c"

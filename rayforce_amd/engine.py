@@ -737,6 +737,81 @@ class Engine:
             raise RfxError("raze: a non-empty list of device columns")
         return self._concat_cols([parts])[0]
 
+    # ------------------------------------------------------------------ upsert, insert (rfx_upsert.hip through rfx_exec_upsert.c)
+    def _upsert(self, table, nkeys, batch, verb):
+        names = list(table)
+        if not names:
+            raise RfxError(f"{verb}: a table with no columns")
+        tcols = [self._check_col(table[k].view(torch.int8) if table[k].dtype == torch.bool else table[k]) for k in names]
+        n = tcols[0].numel()
+        if any(c.numel() != n for c in tcols) or any(c.dtype not in self._CONCAT_DTYPES for c in tcols):
+            raise RfxError(f"{verb}: table columns are equally long tensors of int8 (bool), uint8, int16, int32, int64 or float64")
+        by_name = isinstance(batch, dict)
+        if by_name:  # the DICT / TABLE form: any name order, a missing column is a null vector (matched rows take it too)
+            if not batch or any(k not in table for k in batch):
+                raise RfxError(f"{verb}: a batch name the table does not have")  # reference: err_value
+            given = [batch.get(k) for k in names]
+        else:  # the LIST form: the first l columns; the others keep their matched rows and append their null
+            given = list(batch) + [None] * (len(names) - len(batch))
+            if not batch or len(batch) > len(names) or (not nkeys and len(batch) < len(names)):
+                raise RfxError(f"{verb}: a LIST batch has 1 .. p columns (insert: all p)")  # reference: err_length / a ragged table
+        given = [self._check_col(b.view(torch.int8) if b.dtype == torch.bool else b) if b is not None else None for b in given]
+        lens = {b.numel() for b in given if b is not None}
+        if len(lens) != 1 or 0 in lens:
+            raise RfxError(f"{verb}: batch columns of one length >= 1")
+        m = lens.pop()
+        if nkeys and any(c.dtype == torch.uint8 for c in tcols):
+            raise RfxError("upsert: a uint8 column (the reference answers a LIST column)")
+        if nkeys > min(len(names), L.RFX_MAX_KEYS) or (nkeys < 1 and verb == "upsert"):
+            raise RfxError("upsert: 1 .. 8 keys, no more than the table has columns")
+        descs = (L.UpsertXCol * len(names))()
+        keep = []
+        for i, (t, b) in enumerate(zip(tcols, given)):
+            if b is not None and b.dtype != t.dtype:
+                raise RfxError(f"{verb}: a batch column that is not of its column's dtype")
+            if i < nkeys and (b is None or t.dtype != torch.int64):
+                raise RfxError("upsert: key columns are int64 and the batch provides them")
+            null = {torch.int64: 1 << 63, torch.float64: 0x7FF8000000000000}.get(t.dtype, 0)
+            if b is None and not by_name and t.dtype in (torch.uint8, torch.int16, torch.int32):
+                raise RfxError(f"{verb}: a column not provided whose null is not a cell of its type")  # (the reference answers a LIST column)
+            if b is None and by_name and nkeys:
+                b = torch.full((m,), 0, dtype=t.dtype, device=self.device)
+                L.check(self.lib.rfx_hip_upsert_fill(self._ctx, b.data_ptr(), b.element_size(), null, m), "upsert_fill")
+            keep.append(b)
+            descs[i].d_table, descs[i].d_batch = (t.data_ptr() if n else None), (b.data_ptr() if b is not None else None)
+            descs[i].width, descs[i].null_bits = t.element_size(), null
+            descs[i].role = L.RFX_UPSERT_KEY if i < nkeys else (L.RFX_UPSERT_VALUE if b is not None else L.RFX_UPSERT_ABSENT)
+        a, dest = m, None
+        if nkeys:
+            idx, dest = self.empty(m, torch.int64), self.empty(m, torch.int64)
+            tk = (C.c_void_p * nkeys)(*[descs[i].d_table for i in range(nkeys)])
+            bk = (C.c_void_p * nkeys)(*[descs[i].d_batch for i in range(nkeys)])
+            undefined, appended = C.c_int(0), C.c_int64(0)
+            self._xcheck(self.lib.rfx_exec_upsert_index(self._x, tk, bk, nkeys, n, m, idx.data_ptr(), C.byref(undefined)), "upsert index")
+            self._xcheck(self.lib.rfx_exec_upsert_plan(self._x, idx.data_ptr(), m, n, dest.data_ptr(), C.byref(appended)), "upsert plan")
+            a = int(appended.value)
+            if a < m and any(d.role == L.RFX_UPSERT_VALUE and d.width != 8 for d in descs):
+                raise RfxError("upsert: a matched row for a 1-, 2- or 4-byte value column (the reference answers a LIST column)")
+        outs = [self.empty(n + a, t.dtype) for t in tcols]
+        for i, o in enumerate(outs):
+            descs[i].d_out = o.data_ptr()
+        if nkeys:
+            self._xcheck(self.lib.rfx_exec_upsert_cols(self._x, descs, len(names), dest.data_ptr(), m, n, a), "upsert")
+        else:
+            self._xcheck(self.lib.rfx_exec_insert_cols(self._x, descs, len(names), m, n), "insert")
+        return dict(zip(names, outs))
+
+    def upsert(self, table_columns, nkeys: int, batch_columns) -> Dict[str, torch.Tensor]:
+        """``(upsert t nkeys batch)``: ``table_columns`` a dict of equally long device columns whose first ``nkeys`` are the int64 key; ``batch_columns`` a
+        list of the first l columns' tensors (the others keep their matched rows and append their null) or a dict by name in any order (a missing
+        column is a null vector: matched rows take the null too).  A batch row whose key tuple equals a table row overwrites the FIRST such row's
+        value columns, the last such batch row winning; every other batch row is appended in order.  -> a dict of fresh tensors, the table's names."""
+        return self._upsert(table_columns, int(nkeys), batch_columns, "upsert")
+
+    def insert(self, table_columns, batch_columns) -> Dict[str, torch.Tensor]:
+        """``(insert t batch)``: every batch row appended; the batch as for upsert, a list giving every column.  -> a dict of fresh tensors."""
+        return self._upsert(table_columns, 0, batch_columns, "insert")
+
     def eval_expr(self, expr, table=None) -> torch.Tensor:
         """``(op x y)`` / an expression tree over columns and atoms as a device column: ray_add .. ray_mod (binop_map,
         core/math.c:2280-2345) in ONE pass whatever the depth."""

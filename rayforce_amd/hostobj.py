@@ -66,6 +66,9 @@ OPS_PROTOTYPES = {
     "rfx_concat": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "rfx_raze": (C.c_void_p, [C.c_void_p]),
     "rfx_last_concat_on_gpu": (C.c_int, []),
+    "rfx_upsert": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
+    "rfx_insert": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
+    "rfx_last_upsert_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),
