@@ -1,6 +1,7 @@
 """upsert and insert without a GPU: the numpy restatement (tests/upsert_ref.py) equals every case the compiled reference answered
 (tests/golden/upsert_golden.npz) and a literal per-cell replay of the reference's loop on random small cases; the fixture holds what the issue lists; the
-two verb rows behind rfx_host_fn; every reason the door gives before it needs a device, with its text in rfx_ops_last_error()."""
+two verb rows behind rfx_host_fn; every reason the door gives before it needs a device, with its text in rfx_ops_last_error(); and the restatement of
+the three device calls (plan, place, fill), the reference of tests/test_upsert_edges_gpu.py, pinned to a per-row loop, to the replay and to the fixture."""
 import ctypes as C
 
 import numpy as np
@@ -73,6 +74,50 @@ def test_the_restatement_equals_the_per_cell_replay():
                  m=int(rng.integers(6, 60)), pattern=R.PATTERNS[int(rng.integers(0, 3))], given=given, tdup=int(rng.integers(0, 2)))
         for (tp, attrs, cells), want in zip(R.answer(c), R.replay(c)):
             D.same_column(c["name"], tp, attrs, cells, want)
+
+
+def test_the_plan_equals_its_per_row_loop():
+    """R.plan, the reference of tests/test_upsert_edges_gpu.py: 200 random (n, m, idx), the hostile "none" values among heavily repeated rows"""
+    rng = np.random.default_rng(20261022)
+    for trial in range(200):
+        n, m = int(rng.integers(0, 301)), int(rng.integers(1, 5001))
+        none = np.array(R.HOSTILE + (n, n + 5, 2**62), dtype=np.int64)
+        rows = rng.integers(0, n, m) // int(rng.integers(1, 9)) if n else np.zeros(m, dtype=np.int64)  # (the divisor: heavier repeats)
+        idx = np.where((rng.random(m) < rng.random()) if n else True, none[rng.integers(0, len(none), m)], rows)
+        (dest, a), (want, wa) = R.plan(idx, n), R.plan_loop(idx, n)
+        assert a == wa and dest.dtype == want.dtype and np.array_equal(dest, want), (trial, n, m)
+        hit = (idx >= 0) & (idx < n)
+        assert a == m - int(hit.sum()) and len(set(dest[dest >= 0].tolist())) == int((dest >= 0).sum())  # no destination twice
+    assert R.plan(np.zeros(0, dtype=np.int64), 7)[1] == 0
+
+
+def test_the_scale_patterns_equal_the_per_cell_replay():
+    assert not set(R.SCALE_PATTERNS) & set(R.PATTERNS)
+    for pattern in R.SCALE_PATTERNS:
+        for keys, types in ((1, [R.I64, R.F64, R.I64, R.TS]), (2, [R.I64, R.TS, R.F64, R.I64])):
+            c = dict(name=f"{pattern}_keys{keys}", verb="upsert", keys=keys, form="list", types=types, n=4097, m=4097, pattern=pattern, given=[0, 1, 2, 3])
+            counts = {}
+            for (tp, attrs, cells), want in zip(R.answer(c, counts), R.replay(c)):
+                D.same_column(c["name"], tp, attrs, cells, want)
+            refs = R.batch_refs(pattern, 4097, 4097)
+            assert counts["matched"] == int((refs < 4097).sum()) and 0 < counts["matched"] < 4097
+            assert len(set(refs[refs < 4097].tolist())) == {"hot": 1000, "one": 1}[pattern]
+
+
+def test_every_golden_case_is_rebuilt_from_plan_place_and_fill():
+    ran = 0
+    for c in CASES:
+        if c.get("host"):
+            continue
+        counts, again = {}, {}
+        got = R.rebuilt(c, again)
+        for (tp, attrs, cells), want in zip(got, R.answer(c, counts)):
+            D.same_column(c["name"], tp, attrs, cells, want)
+        assert counts == again and len(got) == len(c["out"]), c["name"]
+        for (tp, attrs, cells), want in zip(got, c["out"]):
+            D.same_column(c["name"], tp, attrs, cells, want)
+        ran += 1
+    assert ran >= 60
 
 
 def test_the_verb_rows_are_bound_by_name(ops):

@@ -18,7 +18,10 @@ The semantics, where the code surprises:
   * a matched row is written by set_idx, which knows I64 / SYMBOL / TIMESTAMP / F64 cells only: it turns a B8 / U8 / I16 / I32 / DATE / TIME value column into
     a LIST; appends keep B8 / I16 / I32 vectors, never DATE / TIME ones, U8 ones under insert's vector forms only.  Those answers are the host's;
   * one record under two or more keys does not find its row in the reference (it indexes a LIST of atoms): the host's;
-  * every column of the answer is a fresh vector of the column's type, attribute byte 0."""
+  * every column of the answer is a fresh vector of the column's type, attribute byte 0.
+
+Further down: the three device calls of include/rfx_hip.h restated (winners, plan, plan_loop, place, fill), a case's answer composed from them as the
+planner composes it (rebuilt), and find's route from the key columns' ranges (find_route) -- the reference of tests/test_upsert_edges_gpu.py."""
 import json
 import os
 
@@ -82,10 +85,15 @@ def batch_refs(pattern, n, m):
         r = np.where(j % 2 == 0, hit, n + j)
         r[[1, 2, 70, m - 1]] = n + 1
         return r
+    if pattern == "hot":  # every batch row on one of 1 000 table rows, every 64th a new key: the contended atomicMax
+        return np.where(j % 64 == 63, n + j, (j * 7919 % 1000) * (n // 1000)) if n else n + j
+    if pattern == "one":  # one address: every even batch row names table row 5, every odd one is new
+        return np.where(j % 2 == 0, 5, n + j) if n > 5 else n + j
     raise KeyError(pattern)
 
 
 PATTERNS = ("all", "none", "alt", "runs", "dups", "newdups")
+SCALE_PATTERNS = ("hot", "one")  # of the tests at scale (tests/test_upsert_edges_gpu.py): not in the fixture, not in its census
 
 
 def inputs(c):
@@ -168,6 +176,101 @@ def replay(c):
                 col[rows[j]] = b[j]
         out.append((tp, 0, np.array(col, dtype=DTYPE[tp])))
     return out
+
+
+# ---- the three device calls of include/rfx_hip.h, restated: rfx_hip_upsert_plan, _place, _fill ----
+HOSTILE = (NULL_I64, -1, -7)  # "none" beside a row >= n: the null and two negatives
+
+
+def winners(idx, n):
+    """per table row the largest batch row that matched it, -1 where none did: what the scratch W holds at the matched rows after k_up_max"""
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    hit = idx.view(np.uint64) < np.uint64(n)
+    w = np.full(n, -1, dtype=np.int64)
+    np.maximum.at(w, idx[hit], np.flatnonzero(hit))
+    return w
+
+
+def plan(idx, n):
+    """rfx_hip_upsert_plan -> (dest, appended): a row is matched iff (uint64)idx[j] < n; dest[j] = idx[j] when j is the largest batch row with that idx, -1
+    when a later one has it, n + (the unmatched rows before j) otherwise"""
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    j = np.arange(len(idx), dtype=np.int64)
+    hit = idx.view(np.uint64) < np.uint64(n)
+    w = winners(idx, n)
+    miss = (~hit).astype(np.int64)
+    dest = n + np.cumsum(miss) - miss  # (the exclusive count)
+    dest[hit] = np.where(w[idx[hit]] == j[hit], idx[hit], -1)
+    return dest, int(miss.sum())
+
+
+def plan_loop(idx, n):
+    """the same, row by row (small m)"""
+    last, dest, a = {}, [], 0
+    for j, r in enumerate(idx):
+        if 0 <= int(r) < n:
+            last[int(r)] = j
+    for j, r in enumerate(idx):
+        if 0 <= int(r) < n:
+            dest.append(int(r) if last[int(r)] == j else -1)
+        else:
+            dest.append(n + a)
+            a += 1
+    return np.array(dest, dtype=np.int64).reshape(len(idx)), a
+
+
+def place(outs, batch, dest, n, total, appends_only):
+    """rfx_hip_upsert_place, in batch order and in place: outs[k][dest[j]] = batch[k][j] where 0 <= dest[j] < total (appends_only[k]: n <= dest[j]);
+    dest None: every row appended in order"""
+    d = n + np.arange(len(batch[0]), dtype=np.int64) if dest is None else np.asarray(dest, dtype=np.int64)
+    for o, b, ao in zip(outs, batch, appends_only):
+        ok = (d >= (n if ao else 0)) & (d < total)
+        o[d[ok]] = b[ok]
+
+
+def fill(width, bits, cells):
+    """rfx_hip_upsert_fill: `cells` cells of the low `width` bytes of `bits`"""
+    return np.full(cells, bits & ((1 << (8 * width)) - 1), dtype={1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[width])
+
+
+def null_bits(tp):
+    """the cell the planner fills for a column the batch does not provide (Engine._upsert), as the bits handed to the fill"""
+    return int(as_bits(np.array([nullv(tp)], dtype=DTYPE[tp]))[0])
+
+
+def rebuilt(c, counts=None):
+    """a case's answer as the planner composes it (rfx_exec_upsert.c upsert_cols): index -> plan -> the table's cells, the fill of the columns not
+    provided, the place -- key columns appends only; a DICT's missing column a filled null vector that is placed as a value column"""
+    table, batch = inputs(c)
+    cols, nulled = ordered(c, batch)
+    n, m, keys = c["n"], c["m"], c["keys"]
+    dest, a = (None, m)
+    if keys:
+        dest, a = plan(index(table, [cols[k] for k in range(keys)], keys), n)
+    if counts is not None:
+        counts.update(matched=m - a, appended=a)
+    outs, placed, given, ao = [], [], [], []
+    for i, tp in enumerate(c["types"]):
+        width = np.dtype(DTYPE[tp]).itemsize
+        o = np.concatenate([table[i], np.zeros(a, dtype=DTYPE[tp])])
+        b = cols[i]
+        if b is None and nulled and keys:
+            b = fill(width, null_bits(tp), m).view(DTYPE[tp])
+        if b is None:
+            o[n:] = fill(width, null_bits(tp), a).view(DTYPE[tp])
+        else:
+            placed.append(o)
+            given.append(b)
+            ao.append(i < keys)
+        outs.append(o)
+    place(placed, given, dest, n, n + a, ao)
+    return [(tp, 0, o) for tp, o in zip(c["types"], outs)]
+
+
+def find_route(table_key, batch_key):
+    """the route rfx_exec_set.c takes for find over one key column: the two scopes' intersection empty -> "disjoint", at most 2^20 wide -> "dense", else "hash" """
+    lo, hi = max(int(table_key.min()), int(batch_key.min())), min(int(table_key.max()), int(batch_key.max()))
+    return "disjoint" if lo > hi else ("dense" if hi - lo + 1 <= 2**20 else "hash")
 
 
 # what a `host_` case builds (tests/upsert_door.py host_call), by name -> (verb, the reason the door gives)
