@@ -131,3 +131,72 @@ def test_python_bindings_declare_them_and_the_host_binds_the_names():
         assert H.header(fn).type == 103 and H.header(fn).attrs == 0, name
         assert C.c_int64.from_address(fn + 8).value == C.cast(getattr(lib, sym), C.c_void_p).value, name
     assert lib.rfx_host_fn(b"last")  # (last column) among the aggregates
+
+
+# ---------------------------------------------------------------------------------------------------- what tests/test_wj_edges_gpu.py stands on
+def test_rows_per_wave_at_its_thresholds():
+    for cus in (256, 64, 32):
+        W = cus * 32
+        for r in (1, 2, 4, 8, 16, 32, 64):
+            lo = R.n_lo(r, cus)
+            assert lo == W * r - r + 1 and R.rows_per_wave(lo, cus, 1) == r, (cus, r)
+            assert -(-lo // r) == W and lo % r == 1 % r  # every wave slot once; the last wave holds one row
+            if r >= 2:
+                assert R.rows_per_wave(W * r - r, cus, 1) == r // 2, (cus, r)
+            if r < 64:
+                assert R.rows_per_wave(R.n_lo(2 * r, cus) - 1, cus, 400) == r, (cus, r)
+            for n in (1, lo - 1, lo, 3 * lo, 64 * W + 65):
+                assert R.rows_per_wave(n, cus, 0) == 64, (cus, n)
+        # the second trips of the wave loop (cus * 32 waves a trip) at 1 and at 64 rows per wave
+        assert R.rows_per_wave(1, cus, 1) == 1 and R.rows_per_wave(W + W // 2 + 1, cus, 1) == 1 and R.rows_per_wave(64 * W + 65, cus, 1) == 64
+    assert 8192 + 8192 // 2 + 1 == 8192 + 4097
+
+
+def exact_cells(dtype, nv, rng):
+    """cells whose f64 sums are exact in every order: I64 multiples of 2^40 within +-2^62 (the I64 sums wrap), F64 multiples of 0.25 below 2^30.
+    5 % nulls, all of them in the column's first half (10 % there) so that long windows of the second half keep a sum, and a run of 40"""
+    null = (rng.random(nv) < 0.1) & (np.arange(nv) < nv // 2)
+    null[100:140] = True
+    if dtype == "i64":
+        v = rng.integers(-(2**22), 2**22, nv) << 40
+        v[null] = R.NULL
+    else:
+        v = rng.integers(-(2**32) + 1, 2**32, nv) * 0.25
+        v[null] = np.nan
+    return v
+
+
+@pytest.mark.parametrize("dtype", ["i64", "f64"])
+def test_fold_direct_equals_the_replay_on_the_edge_windows(dtype):
+    rng = np.random.default_rng(3)
+    nv, n = 1031, 3001
+    li, ri, info = R.edge_windows(nv, n, rng)
+    length = np.where(li < 0, 0, ri - li + 1)
+    # what the set is there for
+    assert set(R.EDGE_LENGTHS) | {nv, nv - 1, nv - 2, nv - 3} <= set(length) and 0 < (length > 16).sum() <= 512
+    for L, Rr in info["edge"]:
+        assert ((li == L) & (ri == Rr)).any(), (L, Rr)
+    assert sorted(info["shuffle"]) != list(info["shuffle"]) and len(set(info["shuffle"])) == n - 256
+    b = info["blocks"]
+    assert all(at % 64 == 0 for at in b.values())
+    assert (length[b["all_long"]:b["all_long"] + 64] > 16).all() and (li[b["all_null"]:b["all_null"] + 64] == -1).all()
+    assert list(np.flatnonzero(length[b["lane0_long"]:b["lane0_long"] + 64] > 16)) == [0]
+    assert list(np.flatnonzero(length[b["lane63_long"]:b["lane63_long"] + 64] > 16)) == [63]
+    assert {0, 1} <= set(li[length > 16] % 2) and {0, 1} <= set(ri[length > 16] % 2) and (ri[length > 16] == nv - 1).any()
+    v = exact_cells(dtype, nv, rng)
+    want, got = R.window_fold(v, li, ri), R.fold_direct(v, li, ri)
+    for a in R.AGGS:
+        assert got[a].dtype == want[a].dtype, a
+        bad = np.flatnonzero(np.ascontiguousarray(got[a]).view(np.int64) != np.ascontiguousarray(want[a]).view(np.int64))
+        assert bad.size == 0, (a, bad[:5], li[bad[:5]], ri[bad[:5]], got[a][bad[:5]], want[a][bad[:5]])
+    summed = ~np.isnan(want["sum"]) if dtype == "f64" else want["sum"] != R.NULL
+    assert (summed & (length > 16)).sum() >= 10 and (~summed & (length > 16)).sum() >= 10 and (summed & (length > 500)).any()
+    if dtype == "i64":
+        assert np.array_equal(R.sum_by_cumsum(v, li, ri), want["sum"])
+        full = want["sum"] != R.NULL
+        assert (np.abs(want["avg"][full & (length > 2)] * length[full & (length > 2)]) > 2.0**63).any()  # some sums wrapped
+        covered = (li >= 100) & (ri < 140)
+        assert covered.any() and (want["min"][covered] == R.INF).all() and (want["max"][covered] == R.NULL).all()
+    else:
+        covered = (li >= 100) & (ri < 140)
+        assert covered.any() and np.isinf(want["min"][covered]).all() and np.isnan(want["max"][covered]).all()

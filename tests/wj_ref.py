@@ -141,3 +141,120 @@ def load_case(gold, ci):
     out = unplanes(gold[f"c{ci}_out"]).reshape(2, 2, len(AGGS), nl)
     c["out"] = [{col: {a: out[w, x, k] for k, a in enumerate(AGGS)} for x, col in enumerate(("vi", "vf"))} for w in (0, 1)]
     return c
+
+
+# ---------------------------------------------------------------------------------------------------- the fold's launch, and windows at its edges
+WAVE, LANE_MAX = 64, 16  # RFX_WAVE, RFX_WINDOW_LANE_MAX (rayforce_amd/csrc/rfx_window.hip)
+EDGE_LENGTHS = (1, 2, 15, 16, 17, 18, 127, 128, 129, 255, 256, 257, 258, 259, 511, 512, 513)
+
+
+def rows_per_wave(n, cus, long_windows):
+    """rfx_hip_window_fold's rule: 64 left rows per wave while every window is a lane's; with long windows as few as it takes to give each of the
+    device's cus * 32 wave slots a wave"""
+    rpw = WAVE
+    if long_windows > 0:
+        while rpw > 1 and (n + rpw - 1) // rpw < cus * 32:
+            rpw >>= 1
+    return rpw
+
+
+def n_lo(r, cus):
+    """the smallest n that runs with r rows per wave (r = 1: the largest); one row less runs with r / 2"""
+    return cus * 32 * r - r + 1
+
+
+def sum_by_cumsum(v, li, ri):
+    """I64 sums a second way: the difference of two wrapping prefix sums, null where the window holds a null cell or is the null row"""
+    v = np.asarray(v, np.int64)
+    isn = v == NULL
+    with np.errstate(over="ignore"):
+        cs = np.concatenate([[0], np.cumsum(np.where(isn, 0, v), dtype=np.int64)])
+        cn = np.concatenate([[0], np.cumsum(isn)])
+        a, b = np.maximum(li, 0), np.maximum(ri + 1, 0)
+        return np.where((li < 0) | (cn[b] - cn[a] > 0), NULL, cs[b] - cs[a])
+
+
+def fold_direct(v, li, ri):
+    """every aggregate of every row from the slice v[li : ri + 1] alone, by the reference's rules stated per window (no code shared with
+    window_fold): count is the window's length; sum is null when a cell is; min over null cells only is INF_I64 / +inf; max and first of an F64
+    window of NaN cells only are the LAST cell's own NaN, last of it the canonical null.  I64 sums wrap; F64 sums, and the f64 sum behind avg, are
+    math.fsum: the exactly rounded sum, which every order of addition gives where the additions are exact.  -> {agg: cells}, as window_fold"""
+    import math
+    f64 = v.dtype == np.float64
+    n = len(li)
+    nullb = NAN_BITS if f64 else NULL & (2**64 - 1)
+    bits = v.view(np.uint64)
+    out = {a: np.full(n, nullb, np.uint64) for a in AGGS if a not in ("count", "avg")}
+    cnt, avg = np.zeros(n, np.int64), np.full(n, np.nan)
+    for i in range(n):
+        if li[i] < 0:
+            continue
+        w, wb = v[li[i]:ri[i] + 1], bits[li[i]:ri[i] + 1]
+        cnt[i] = len(w)
+        ok = ~np.isnan(w) if f64 else w != NULL
+        cells, cb = w[ok], wb[ok]
+        if len(cells) == 0:
+            out["min"][i] = np.array([np.inf]).view(np.uint64)[0] if f64 else INF
+            if f64:
+                out["max"][i] = out["first"][i] = wb[-1]
+            continue
+        try:
+            fs = math.fsum(float(x) for x in cells) + 0.0  # (the reference's chain starts at +0.0: cells of -0.0 only sum to +0.0)
+        except (ValueError, OverflowError):  # (+inf and -inf in one window)
+            fs = math.nan
+        avg[i] = fs / len(cells) if fs == fs else math.nan
+        if len(cells) == len(w):
+            out["sum"][i] = np.array([fs]).view(np.uint64)[0] if f64 else sum(int(x) for x in cells) & (2**64 - 1)
+        out["min"][i], out["max"][i] = cb[np.argmin(cells)], cb[np.argmax(cells)]
+        out["first"][i], out["last"][i] = cb[0], cb[-1]
+    res = {a: c.view(v.dtype) for a, c in out.items()}
+    res["count"], res["avg"] = cnt, avg
+    return {a: res[a] for a in AGGS}
+
+
+def edge_windows(nv, n, rng):
+    """(li, ri, info): n windows over a column of nv cells, every position valid (0 <= li <= ri < nv, or (-1, -2)), at most 512 of them longer than
+    a lane's 16 cells.  Four blocks of 64 consecutive rows at multiples of 64 -- all long; only the first row long; only the last; all null -- and,
+    shuffled over the other rows (info["shuffle"]: the row of each window of the fixed order), every L in 0 .. 3 and every L with R == nv - 1
+    crossed with EDGE_LENGTHS and nv - L, then 10 % null rows and windows of 1 .. 16 cells at a random L"""
+    assert nv >= 600 and n >= 16 * WAVE
+    edge = []
+    for length in EDGE_LENGTHS:
+        edge += [(L, L + length - 1) for L in (0, 1, 2, 3)] + [(nv - length, nv - 1)]
+    edge += [(L, nv - 1) for L in (0, 1, 2, 3)]
+    blocks = {"all_long": 2 * WAVE, "lane0_long": 5 * WAVE, "lane63_long": 9 * WAVE, "all_null": 12 * WAVE}
+    nrest = n - 4 * WAVE
+    assert nrest >= len(edge)
+
+    def short(m):
+        length = rng.integers(1, LANE_MAX + 1, m)
+        L = rng.integers(0, nv - LANE_MAX, m)
+        return L, L + length - 1
+
+    def long_(m):
+        length = rng.integers(LANE_MAX + 1, 600, m)
+        L = rng.integers(0, nv - 600, m)
+        return L, L + length - 1
+
+    fl, fr = short(nrest)
+    null = rng.random(nrest) < 0.1
+    fl[null], fr[null] = -1, -2
+    fl[:len(edge)], fr[:len(edge)] = np.array(edge, np.int64).T
+    shuffle = rng.permutation(nrest)
+    li, ri = np.empty(n, np.int64), np.empty(n, np.int64)
+    free = np.ones(n, bool)
+    for at in blocks.values():
+        free[at:at + WAVE] = False
+    rows = np.flatnonzero(free)[shuffle]
+    li[rows], ri[rows] = fl, fr
+    at = blocks["all_long"]
+    li[at:at + WAVE], ri[at:at + WAVE] = long_(WAVE)
+    for name, lane in (("lane0_long", 0), ("lane63_long", WAVE - 1)):
+        at = blocks[name]
+        li[at:at + WAVE], ri[at:at + WAVE] = short(WAVE)
+        li[at + lane], ri[at + lane] = (x[0] for x in long_(1))
+    at = blocks["all_null"]
+    li[at:at + WAVE], ri[at:at + WAVE] = -1, -2
+    length = np.where(li < 0, 0, ri - li + 1)
+    assert (((li >= 0) & (li <= ri) & (ri < nv)) | ((li == -1) & (ri == -2))).all() and 0 < int((length > LANE_MAX).sum()) <= 512
+    return li, ri, {"shuffle": rows, "blocks": blocks, "edge": edge}
