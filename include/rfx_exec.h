@@ -391,6 +391,29 @@ int rfx_exec_upsert_plan(rfx_exec_t *x, const int64_t *d_idx, int64_t m, int64_t
 int rfx_exec_upsert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, const int64_t *d_dest, int64_t m, int64_t n, int64_t appended);
 int rfx_exec_insert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, int64_t m, int64_t n);
 
+/* ---- row, collect (rfx_collect.hip; aggr_row / aggr_collect, core/aggr.c:3021-3136): every group's rows and cells, in group order ----
+ * rfx_exec_group_partition: m elements with the dense group ids d_gid[i] in [0, groups) (element-aligned: element i is table row i, or row d_rows[i] of a
+ *   filter) -> out->d_perm (m cells: the elements ordered by (group, element), stable) and out->d_offsets (groups + 1 cells: group g's elements are
+ *   d_perm[d_offsets[g] .. d_offsets[g + 1])), both on shard 0, released by rfx_exec_group_partition_free.  The ids are checked on the device before
+ *   anything is placed: one outside [0, groups) answers RFX_EINVAL ("a group id outside [0, groups)") and is never used as an index.  Returns with the
+ *   stream idle.  m, groups < 2^31 (RFX_ELIMIT); scratch 20 B per element, freed before return; RFX_ENOMEM when it does not fit.
+ * rfx_exec_group_collect: d_outs[k][j] = d_cols[k][src(j)] for j < part->m, src(j) = d_rows ? d_rows[d_perm[j]] : d_perm[j]; widths[k] = the bytes of
+ *   column k's cells (1, 2, 4 or 8), the output in the same width, cell-aligned; want_rows: d_rows_out[j] = src(j) as i64 as well (`row`).  The columns hold
+ *   col_len cells; d_rows (the filter's row ids, from outside) is checked against it first: one outside answers RFX_EINVAL and nothing is gathered.
+ *   RFX_MAX_COLS outputs to a launch, more in further launches over the same permutation.  Enqueued on shard 0's context (no sync without d_rows).
+ * One shard, one rank: several answer RFX_ELIMIT, "collect over a sharded table".
+ * RFX_XSTAT_COLLECT_PARTITIONS / _COLLECT_PASSES count the partitions and the radix passes they ran, RFX_XSTAT_COLLECTS / _COLLECT_LAUNCHES the collect
+ * calls and their gather launches. */
+typedef struct rfx_partition {
+    int64_t m, groups;
+    int64_t *d_offsets; /* groups + 1 cells */
+    int64_t *d_perm;    /* m cells (NULL when m == 0) */
+} rfx_partition_t;
+int rfx_exec_group_partition(rfx_exec_t *x, const int64_t *d_gid, int64_t m, int64_t groups, rfx_partition_t *out);
+void rfx_exec_group_partition_free(rfx_exec_t *x, rfx_partition_t *p);
+int rfx_exec_group_collect(rfx_exec_t *x, const rfx_partition_t *part, const int64_t *d_rows, int64_t col_len, const void *const *d_cols, const int32_t *widths,
+                           int ncols, void *const *d_outs, int want_rows, int64_t *d_rows_out);
+
 /* ---- counters since rfx_exec_create ---- */
 enum {
     RFX_XSTAT_SCOPE_SAMPLED = 0, /* group-bys that ran under a sampled key scope */
@@ -450,7 +473,11 @@ enum {
     RFX_XSTAT_NS_UPSERT_INDEX = 48, /* wall time of the upserts' index step, nanoseconds, to the stream idle */
     RFX_XSTAT_NS_UPSERT_PLAN = 49,  /* ... of their plan step */
     RFX_XSTAT_NS_UPSERT_PLACE = 50, /* ... and of the copy, fill and place */
-    RFX_XSTAT_N = 51
+    RFX_XSTAT_COLLECT_PARTITIONS = 51, /* group partitions answered by the device path */
+    RFX_XSTAT_COLLECT_PASSES = 52,     /* ... radix passes they ran (a digit every group id agrees on costs none) */
+    RFX_XSTAT_COLLECTS = 53,           /* row / collect calls over a partition */
+    RFX_XSTAT_COLLECT_LAUNCHES = 54,   /* ... gather launches they took (RFX_MAX_COLS outputs to a launch) */
+    RFX_XSTAT_N = 55
 };
 /* what ONE phase hand-over to nshards - 1 worker threads costs the calling thread (microseconds; a bare pool without devices, `reps` empty
  * phases) -- the planner's own overhead per phase of a sharded query, which a one-GPU box can measure */

@@ -909,6 +909,32 @@ int rfx_hip_upsert_plan(rfx_ctx_t *ctx, const int64_t *d_idx, int64_t m, int64_t
 int rfx_hip_upsert_place(rfx_ctx_t *ctx, const rfx_upsert_col_t *cols, int ncols, const int64_t *d_dest, int64_t m, int64_t n, int64_t total);
 int rfx_hip_upsert_fill(rfx_ctx_t *ctx, void *d_dst, int32_t width, uint64_t bits, int64_t cells);
 
+/* ---- row, collect (rfx_collect.hip): the members of every group (aggr_row / aggr_collect, core/aggr.c:3021-3136) ----
+ * rfx_hip_ids_check: *bad = how many of d_ids[0 .. m) lie outside [0, bound) (the null and negatives included).  One pass, one 8-byte read-back (syncs).
+ *   For ids that come from OUTSIDE the library and are about to be used as indexes: a caller refuses the whole input when *bad != 0.
+ * rfx_hip_group_partition: the stable partition of the positions 0 .. m-1 by their dense group id d_gid[i] in [0, groups): d_perm[m] = the positions
+ *   ordered by (group, position), d_offsets[groups + 1] = the exclusive scan of the group sizes (group g's positions are d_perm[d_offsets[g] ..
+ *   d_offsets[g + 1]); a group without rows has an empty range).  The ids are CHECKED first (rfx_hip_ids_check): one outside [0, groups) ends the call
+ *   with RFX_EINVAL before anything is placed -- it is never used as an index.  The order is the packed radix sort's over gid << 32 | position
+ *   (rfx_hip_sort_index, the widened 32-bit key form): a digit every id agrees on costs no pass, so groups <= 256 is one pass, <= 65 536 two (*passes,
+ *   may be NULL); stable and free of atomics on the placement, so the same input gives the same bits.  The offsets are read off the run boundaries of
+ *   the sorted ids.  m < 2^31 and groups < 2^31 (RFX_ELIMIT).  Scratch: the sort's 16 B per position, freed before return (syncs); RFX_ENOMEM
+ *   when it does not fit.  d_gid, d_perm 16-byte aligned.
+ * rfx_hip_group_collect: for j < m and every column k: d_out_k[j] = d_col_k[src(j)], src(j) = d_rows ? d_rows[d_perm[j]] : d_perm[j] -- 1 ..
+ *   RFX_MAX_COLS columns per launch, cells of 1, 2, 4 or 8 bytes, written in the column's own width.  A column with d_col == NULL is the identity:
+ *   d_out[j] = src(j) as i64 (`row`; width 8).  d_perm (and d_rows through it) is read once per launch into LDS, not once per column; every output is
+ *   written in whole 16-byte stores between a head and a tail of single cells, whatever its base (cell-aligned, nothing more).  col_len = the cells every
+ *   column holds: a src outside [0, col_len) -- which checked inputs never produce -- is not read, its cell is 0.  d_perm 16-byte aligned. */
+typedef struct {
+    const void *d_col; /* NULL: the identity column */
+    void *d_out;
+    int32_t width;
+    int32_t _pad;
+} rfx_collect_col_t;
+int rfx_hip_ids_check(rfx_ctx_t *ctx, const int64_t *d_ids, int64_t m, int64_t bound, int64_t *bad);
+int rfx_hip_group_partition(rfx_ctx_t *ctx, const int64_t *d_gid, int64_t m, int64_t groups, int64_t *d_offsets, int64_t *d_perm, int32_t *passes);
+int rfx_hip_group_collect(rfx_ctx_t *ctx, const rfx_collect_col_t *cols, int ncols, const int64_t *d_perm, const int64_t *d_rows, int64_t m, int64_t col_len);
+
 /* ---- hash primitives pinned against the reference (core/hash.c:530-542, core/hash.h:86-97) ---- */
 int rfx_hip_hash_fnv1a_i64(rfx_ctx_t *ctx, const int64_t *d_in, int64_t n, uint64_t *d_out);
 int rfx_hip_hash_mix_u64(rfx_ctx_t *ctx, const uint64_t *d_in, int64_t n, uint64_t seed_or_prev, uint64_t *d_out);

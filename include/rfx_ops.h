@@ -46,6 +46,7 @@
  *   rfx_union              ray_union             core/items.c:1022               binary_f  (x, y) -> distinct of x followed by y, ATTR_DISTINCT
  *   rfx_concat             ray_concat            core/compose.c:465-823          binary_f  (x, y) vectors of one type, a vector and an atom, two tables -> x's cells, then y's
  *   rfx_raze               ray_raze              core/compose.c:1096-1164        unary_f   LIST of vectors of one type -> their cells end to end
+ *   rfx_row                ray_row               core/compose.c:1166-1169        unary_f   MAPGROUP(val, index) -> LIST of one I64 vector of row numbers per group
  *
  * Everything below runs on the MI355X through the flat ABI of rfx_hip.h.  There is NO CPU implementation behind these
  * entry points: queries whose shape the GPU path does not cover are handed back to the host's own ray_* function when
@@ -319,6 +320,26 @@ rfx_obj_p rfx_upsert(rfx_obj_p *x, int64_t n);
 rfx_obj_p rfx_insert(rfx_obj_p *x, int64_t n);
 /* 1: the last of those two calls was answered by the device path; 0: it went to the host or failed */
 int rfx_last_upsert_on_gpu(void);
+
+/* The nested results of select ... by: (rfx_collect.hip): every group's rows and cells as a LIST of `groups` vectors, attribute byte 0, groups in the
+ * index's own order, every vector in visiting order (AGGR_ITER, core/aggr.c:73-125: one thread, so the answer does not depend on the pool).
+ *   rfx_row      ray_row (core/compose.c:1166-1169 -> aggr_row, core/aggr.c:3118-3136; FN_AGGR): a MAPGROUP (val, index) pair -> one I64 vector of row
+ *                numbers per group; val's cells are never read.
+ *   rfx_collect  aggr_collect (core/aggr.c:3021-3116), which the reference reaches through select / update only -- declared for the standalone host, the
+ *                tests and rfx_select: the same pairs over a value column of type B8 U8 I16 I32 DATE TIME I64 SYMBOL TIMESTAMP F64 -> one vector of that
+ *                type per group.
+ * The index is INDEX_TYPE_IDS or INDEX_TYPE_SHIFT, with or without filter ids.  The device builds ONE buffer in group order plus the offsets (a stable
+ * partition by group id, then a gather), both are read back once, the host cuts the vectors out with a memcpy each.  groups == 0 or no element: `groups`
+ * empty vectors, no launch.
+ * Handed to the host's own ray_row (rfx_collect, and both without a host: refused with the reason, also in rfx_ops_last_error()): parted / window
+ * indexes; ENUM / GUID / LIST / C8 / parted value columns; a plain vector or a MAPFILTER pair; more than one shard ("collect over a sharded table");
+ * 2^31 or more elements; a result the device has no room for; 4-byte and narrower device-column handles.
+ * A malformed index is an error of ours, as for the grouped aggregates: wrong slot count, ids / filter length mismatch, an id outside [0, groups), a source
+ * cell outside the SHIFT table, a filter id outside the column -- checked on the device before any of them is used as an index. */
+rfx_obj_p rfx_row(rfx_obj_p x);
+rfx_obj_p rfx_collect(rfx_obj_p x);
+/* 1: the last of those two calls was answered by the device path (an empty answer included: no launch); 0: it went to the host or failed */
+int rfx_last_collect_on_gpu(void);
 
 /* ---- residency ---------------------------------------------------------------------------------------------------- */
 /* unary_f: (update {col: mapping ... from: t [where: p] [by: k]}) -- ray_update, core/update.c:936-1106: a NEW table whose named columns

@@ -144,6 +144,7 @@ RFX_XSTAT_CONCATS, RFX_XSTAT_CONCAT_SPANS, RFX_XSTAT_CONCAT_CELLS = 41, 42, 43
 RFX_XSTAT_UPSERTS, RFX_XSTAT_UPSERT_MATCHED, RFX_XSTAT_UPSERT_APPENDED, RFX_XSTAT_INSERTS = 44, 45, 46, 47
 RFX_XSTAT_NS_UPSERT_INDEX, RFX_XSTAT_NS_UPSERT_PLAN, RFX_XSTAT_NS_UPSERT_PLACE = 48, 49, 50
 RFX_UPSERT_KEY, RFX_UPSERT_VALUE, RFX_UPSERT_ABSENT = 0, 1, 2
+RFX_XSTAT_COLLECT_PARTITIONS, RFX_XSTAT_COLLECT_PASSES, RFX_XSTAT_COLLECTS, RFX_XSTAT_COLLECT_LAUNCHES = 51, 52, 53, 54
 RFX_MERGE_MAX_RUNS = 16
 # include/rfx_hip.h RFX_CAST_*: the reference's vector type codes rfx_hip_cast / rfx_exec_cast take
 RFX_CAST = {"b8": 1, "u8": 2, "i16": 3, "i32": 4, "i64": 5, "date": 7, "time": 8, "timestamp": 9, "f64": 10}
@@ -174,6 +175,14 @@ class UpsertCol(C.Structure):  # rfx_upsert_col_t
 
 class UpsertXCol(C.Structure):  # rfx_upsert_xcol_t
     _fields_ = [("d_table", C.c_void_p), ("d_batch", C.c_void_p), ("d_out", C.c_void_p), ("width", C.c_int32), ("role", C.c_int32), ("null_bits", C.c_uint64)]
+
+
+class CollectCol(C.Structure):  # rfx_collect_col_t
+    _fields_ = [("d_col", C.c_void_p), ("d_out", C.c_void_p), ("width", C.c_int32), ("_pad", C.c_int32)]
+
+
+class Partition(C.Structure):  # rfx_partition_t
+    _fields_ = [("m", C.c_int64), ("groups", C.c_int64), ("d_offsets", C.c_void_p), ("d_perm", C.c_void_p)]
 
 
 class QCol(C.Structure):
@@ -358,6 +367,9 @@ PROTOTYPES = {
     "rfx_hip_upsert_plan": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int64)]),
     "rfx_hip_upsert_place": (C.c_int, [_ctx, _P(UpsertCol), C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
     "rfx_hip_upsert_fill": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64]),
+    "rfx_hip_ids_check": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "rfx_hip_group_partition": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "rfx_hip_group_collect": (C.c_int, [_ctx, _P(CollectCol), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "rfx_hip_seg_search": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "rfx_hip_asof_runs": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "rfx_hip_set_scope": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_int64)]),
@@ -453,6 +465,9 @@ EXEC_PROTOTYPES = {
     "rfx_exec_upsert_plan": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int64)]),
     "rfx_exec_upsert_cols": (C.c_int, [_exec, _P(UpsertXCol), C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
     "rfx_exec_insert_cols": (C.c_int, [_exec, _P(UpsertXCol), C.c_int, C.c_int64, C.c_int64]),
+    "rfx_exec_group_partition": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_int64, _P(Partition)]),
+    "rfx_exec_group_partition_free": (None, [_exec, _P(Partition)]),
+    "rfx_exec_group_collect": (C.c_int, [_exec, _P(Partition), C.c_void_p, C.c_int64, _P(C.c_void_p), _P(C.c_int32), C.c_int, _P(C.c_void_p), C.c_int, C.c_void_p]),
     "rfx_exec_asof_index": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, _P(C.c_int)]),
     "rfx_exec_bin": (C.c_int, [_exec, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "rfx_exec_window_ranges": (C.c_int, [_exec, _P(C.c_void_p), _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,

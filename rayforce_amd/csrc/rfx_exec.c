@@ -96,3 +96,4 @@ static inline int64_t now_ns(void) {
 #include "rfx_exec_cast.c"
 #include "rfx_exec_concat.c"
 #include "rfx_exec_upsert.c"
+#include "rfx_exec_collect.c"

@@ -111,7 +111,8 @@ void rfx_host_trim(void);
     V(F_CONCAT, "ray_concat", rfx_concat, "concat", RFX_TYPE_BINARY, RFX_FN_NONE)                     \
     V(F_RAZE, "ray_raze", rfx_raze, "raze", RFX_TYPE_UNARY, RFX_FN_NONE)                              \
     V(F_UPSERT, "ray_upsert", rfx_upsert, "upsert", RFX_TYPE_VARY, RFX_FN_NONE)                       \
-    V(F_INSERT, "ray_insert", rfx_insert, "insert", RFX_TYPE_VARY, RFX_FN_NONE)
+    V(F_INSERT, "ray_insert", rfx_insert, "insert", RFX_TYPE_VARY, RFX_FN_NONE)                       \
+    V(F_ROW, "ray_row", rfx_row, "row", RFX_TYPE_UNARY, RFX_FN_AGGR)
 #define V(id, host, ours, name, type, attrs) id,
 enum { RFX_VERBS(V) F_N };
 #undef V
@@ -248,3 +249,4 @@ static int fn_id(obj_p o) {
 #include "rfx_ops_cast.c"
 #include "rfx_ops_concat.c"
 #include "rfx_ops_upsert.c"
+#include "rfx_ops_collect.c"

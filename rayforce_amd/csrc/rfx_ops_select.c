@@ -23,8 +23,10 @@ static void tm_print(void) {
 /* ---- rfx_select, piece by piece.  Every piece answers SEL_GO (carry on), SEL_OUT (*why says which shape the host must answer) or
  * SEL_DONE (an error / a finished result: the caller stops). ---- */
 enum { SEL_GO = 0, SEL_OUT = 1, SEL_DONE = 2 };
+static size_t cell_bytes(int type); /* rfx_ops_operators.c */
 /* the output mappings {name: (aggr column | expression)} of a select dict (everything but from: where: by: take:) as aggregate
  * descriptors over resident device columns */
+#define SEL_NEST 16 /* nested columns of one query, beside its RFX_MAX_AGGS aggregates (more: the host's) */
 #define SEL_AGGS (2 * RFX_MAX_AGGS + 1) /* the query's own + the hidden ones of the reproducible sums: a second limb per rewritten aggregate, one COUNT */
 typedef struct {
     rfx_agg_t aggs[SEL_AGGS];
@@ -47,6 +49,13 @@ typedef struct {
     unsigned char dev[RFX_MAX_AGGS];
     int ndev;
     int nlast; /* (last column) mappings: RFX_AGG_LAST */
+    /* the nested results under by: (rfx_ops_collect.c): a bare column (aggr_collect) or (row column) (aggr_row) -- a LIST column of one vector per group.
+     * They are no aggregates of the planner's: slot[] keeps the result's column order -- a >= 0: aggregate a; -(c + 1): nested column c -- and lists[c]
+     * receives the finished LIST before the table is built */
+    struct { int64_t name; obj_p col; int row; } nest[SEL_NEST];
+    int nnest;
+    signed char slot[RFX_MAX_AGGS + SEL_NEST];
+    obj_p lists[SEL_NEST];
 } sel_maps_t;
 /* result cells of an aggregate over a widened 4-byte column, back in the column's own width: the i64 null and the i64 identities of an
  * all-null group (core/aggr.c:1246) become the 4-byte ones */
@@ -71,11 +80,29 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
     memset(M->dev, 0, sizeof(M->dev));
     M->ndev = 0;
     M->nlast = 0;
+    M->nnest = 0;
+    memset(M->lists, 0, sizeof(M->lists));
     for (int64_t i = 0; i < dkeys->len; i++) {
         int64_t k = RFX_AS_I64(dkeys)[i];
         if (k == s_from || k == s_where || k == s_by || k == s_take) continue;
         obj_p e = RFX_AS_LIST(dvals)[i];
         const int n = M->nagg;
+        /* under by: a bare column symbol is collected and (row column) numbers the rows, per group (core/query.c:439-443, core/compose.c:1166-1169): taken
+         * when the column is one collect reads (select_impl checks the rest of the shape); everything else about them goes where it went */
+        const int bare = e->type == -RFX_TYPE_SYMBOL;
+        const int rowf = e->type == RFX_TYPE_LIST && e->len == 2 && fn_id(RFX_AS_LIST(e)[0]) == F_ROW && RFX_AS_LIST(e)[1]->type == -RFX_TYPE_SYMBOL;
+        if (grouped && (bare || rowf) && M->nnest < SEL_NEST) {
+            obj_p c = table_col(tab, bare ? e->i64 : RFX_AS_LIST(e)[1]->i64);
+            if (c && c->type > 0 && !(g_npx && proxy_of(c)) && !IS_PARTED_TYPE(c->type) && (rowf || c->type == RFX_TYPE_SYMBOL || cell_bytes(c->type)) &&
+                !(c->mmod == RFX_MMOD_DEVICE && !rowf && !col_ctype(c) && c->type != RFX_TYPE_B8)) {
+                M->slot[M->nagg + M->nnest] = (signed char)-(M->nnest + 1);
+                M->nest[M->nnest].name = k;
+                M->nest[M->nnest].col = c;
+                M->nest[M->nnest].row = rowf;
+                M->nnest++;
+                continue;
+            }
+        }
         if (n >= RFX_MAX_AGGS || e->type != RFX_TYPE_LIST || e->len != 2) { *why = "mapping shape"; return SEL_OUT; }
         int f = fn_id(RFX_AS_LIST(e)[0]);
         obj_p a = RFX_AS_LIST(e)[1];
@@ -101,6 +128,7 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
             M->outtype[n] = RFX_TYPE_F64;
             M->med[n] = 1;
             M->nmed++;
+            M->slot[M->nagg + M->nnest] = (signed char)n;
             M->names[M->nagg++] = k;
             continue;
         }
@@ -125,6 +153,7 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
             M->outtype[n] = RFX_TYPE_F64;
             M->dev[n] = 1;
             M->ndev++;
+            M->slot[M->nagg + M->nnest] = (signed char)n;
             M->names[M->nagg++] = k;
             continue;
         }
@@ -146,6 +175,7 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
             M->aggs[n].xnodes = M->xnodes[n];
             M->aggs[n].col_type = RFX_I64;
             M->outtype[n] = (f == F_AVG || rfx_agg_input_type(&M->aggs[n]) == RFX_F64) ? RFX_TYPE_F64 : RFX_TYPE_I64;
+            M->slot[M->nagg + M->nnest] = (signed char)n;
             M->names[M->nagg++] = k;
             continue;
         }
@@ -164,6 +194,7 @@ static int sel_mappings(obj_p tab, obj_p dkeys, obj_p dvals, int grouped, sel_ma
         M->aggs[n].d_col = d;
         M->aggs[n].col_type = narrow ? RFX_I64 : col_ctype(c);
         M->outtype[n] = (f == F_AVG) ? RFX_TYPE_F64 : (f == F_COUNT) ? RFX_TYPE_I64 : c->type;
+        M->slot[M->nagg + M->nnest] = (signed char)n;
         M->names[M->nagg++] = k;
     }
     return SEL_GO;
@@ -548,20 +579,28 @@ static obj_p sel_build_groups(const rfx_groups_t *R, const sel_maps_t *M, const 
     if (!ok || enum_out) {
         for (int i = 0; i < nkeys; i++) if (okcols[i]) H.drop(okcols[i]);
         for (int a = 0; a < nagg; a++) if (ocols[a]) H.drop(ocols[a]);
+        for (int c = 0; c < M->nnest; c++) if (M->lists[c]) H.drop(M->lists[c]);
         if (enum_out) {
             *why = "by: enum column whose domain cannot be resolved";
             return NULL;
         }
         return fail_hip("group-by result");
     }
-    obj_p rk = H.vector(RFX_TYPE_SYMBOL, nagg + nkeys), rv = H.vector(RFX_TYPE_LIST, nagg + nkeys);
+    const int nout = nagg + M->nnest; /* the mappings in the dict's order: aggregates and nested columns side by side */
+    obj_p rk = H.vector(RFX_TYPE_SYMBOL, nout + nkeys), rv = H.vector(RFX_TYPE_LIST, nout + nkeys);
     for (int i = 0; i < nkeys; i++) {
         RFX_AS_I64(rk)[i] = knames[i];
         RFX_AS_LIST(rv)[i] = okcols[i] ? okcols[i] : H.vector(nkeys == 1 ? K->key_out_type : K->kcs[i]->type, 0);
     }
-    for (int a = 0; a < nagg; a++) {
-        RFX_AS_I64(rk)[a + nkeys] = M->names[a];
-        RFX_AS_LIST(rv)[a + nkeys] = ocols[a] ? ocols[a] : H.vector((int8_t)M->outtype[a], 0);
+    for (int p = 0; p < nout; p++) {
+        const int a = M->nnest ? M->slot[p] : p;
+        if (a >= 0) {
+            RFX_AS_I64(rk)[p + nkeys] = M->names[a];
+            RFX_AS_LIST(rv)[p + nkeys] = ocols[a] ? ocols[a] : H.vector((int8_t)M->outtype[a], 0);
+        } else {
+            RFX_AS_I64(rk)[p + nkeys] = M->nest[-a - 1].name;
+            RFX_AS_LIST(rv)[p + nkeys] = M->lists[-a - 1] ? M->lists[-a - 1] : H.vector(RFX_TYPE_LIST, 0);
+        }
     }
     return H.table(rk, rv);
 }
@@ -581,6 +620,7 @@ static obj_p sel_build_scalar(const rfx_value_t *vals, const sel_maps_t *M) {
     return H.table(rk, rv);
 }
 
+static int sel_nested(sel_maps_t *M, const rfx_query_t *Q, const void *dkey, const rfx_groups_t *R, obj_p *res, const char **why); /* rfx_ops_collect.c */
 static obj_p select_impl(obj_p dict) {
     rfx_host_bind();
     g_ntm = 0;
@@ -697,6 +737,16 @@ static obj_p select_impl(obj_p dict) {
              * so that this entry point never answers differently from ray_select. */
             if (nkeys > 1 && where) { why = "where: with several by: columns"; goto out; }
         }
+        if (M.nnest) {
+            /* nested columns: ONE plain I64 / SYMBOL / TIMESTAMP key without xbar, an in-memory table whole on one device, one process; every other shape
+             * goes where it went before these mappings were read (a bare column: "mapping shape"; (row column): no aggregate) */
+            int bare = 0;
+            for (int c = 0; c < M.nnest; c++) bare |= !M.nest[c].row;
+            if (nkeys != 1 || kxbar[0] || parted || kenum || !kcs[0] || kcs[0]->type == RFX_TYPE_F64 || g_nshards > 1 || rfx_exec_ranks(g_x, NULL) > 1 || nrows >= 0x80000000LL) {
+                why = bare ? "mapping shape" : "mapping is not (aggr ...)";
+                goto out;
+            }
+        }
         rfx_query_t Q;
         memset(&Q, 0, sizeof(Q));
         Q.preds = wp.preds;
@@ -770,6 +820,14 @@ static obj_p select_impl(obj_p dict) {
             if (grc == RFX_ELIMIT && g_nshards > 1) { why = M.nlast ? "sharded table: last under by: runs on the shards of one device" : "sharded table: shape the planner runs on one shard"; goto out; }
             if (grc != RFX_OK) { res = fail(rfx_exec_last_error(g_x)); goto done; }
             const sel_keys_t K = {nkeys, key_out_type, kenum, kcs};
+            if (M.nnest) { /* the members of every group, in the order the aggregates' columns come out in: the groups' own keys name the places */
+                const int crc = sel_nested(&M, &Q, dks[0], &R, &res, &why);
+                if (crc != SEL_GO) {
+                    rfx_exec_groups_free(g_x, &R);
+                    if (crc == SEL_OUT) goto out;
+                    goto done;
+                }
+            }
             rfx_groups_t Rw;
             const rfx_groups_t *Ru = &R;
             if (rank_slices_mode()) { /* this rank's range of the groups only */

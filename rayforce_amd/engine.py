@@ -812,6 +812,96 @@ class Engine:
         """``(insert t batch)``: every batch row appended; the batch as for upsert, a list giving every column.  -> a dict of fresh tensors."""
         return self._upsert(table_columns, 0, batch_columns, "insert")
 
+    # ------------------------------------------------------------------ row, collect (rfx_collect.hip through rfx_exec_collect.c)
+    def _partition(self, gid: torch.Tensor, groups: int):
+        gid = self._check_col(gid)
+        if gid.dtype != torch.int64:
+            raise RfxError("partition: group ids are int64")
+        part = L.Partition()
+        m = gid.numel()
+        self._xcheck(self.lib.rfx_exec_group_partition(self._x, gid.data_ptr() if m else None, m, int(groups), C.byref(part)), "partition")
+        return part, _Owner(self, part, self.lib.rfx_exec_group_partition_free)
+
+    def partition(self, gid: torch.Tensor, groups: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The stable partition of the positions 0 .. m-1 by their dense group id ``gid[i]`` in [0, groups) -> (offsets, perm): ``perm`` the positions
+        ordered by (group, position), group g's at ``perm[offsets[g]:offsets[g + 1]]`` (rfx_exec_group_partition).  An id outside [0, groups) is refused
+        before anything is placed.  One shard.  (syncs)"""
+        part, own = self._partition(gid, groups)
+        return self._view(own, part.d_offsets, int(groups) + 1, torch.int64), self._view(own, part.d_perm, int(part.m), torch.int64)
+
+    _COLLECT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64, torch.float64)
+
+    def partition_collect(self, gid: torch.Tensor, groups: int, columns, rows: Optional[torch.Tensor] = None, outs=None, want_rows: bool = False,
+                          col_len: Optional[int] = None):
+        """The two primitives over the caller's own group ids: partition ``gid`` (one id per element), then ``outs[k][j] = columns[k][src(j)]`` with
+        ``src(j) = rows[perm[j]]`` under a filter's row ids, else ``perm[j]`` -> (offsets, [cells per column], rows or None).  ``outs``: the caller's
+        own result tensors (cell-aligned views included), else fresh ones.  (syncs)"""
+        cols = [self._check_col(c.view(torch.int8) if c.dtype == torch.bool else c) for c in columns]
+        if any(c.dtype not in self._COLLECT_DTYPES for c in cols) or len({c.numel() for c in cols}) > 1:
+            raise RfxError("collect: columns are equally long tensors of int8 (bool), uint8, int16, int32, int64 or float64")
+        part, own = self._partition(gid, groups)
+        m = int(part.m)
+        if rows is not None and (self._check_col(rows, m).dtype != torch.int64):
+            raise RfxError("collect: row ids are int64")
+        n = cols[0].numel() if cols else (m if col_len is None else int(col_len))  # (the cells a row id may name)
+        outs = [self.empty(m, c.dtype) for c in cols] if outs is None else [self._check_col(o, m) for o in outs]
+        if len(outs) != len(cols) or any(o.dtype != c.dtype for o, c in zip(outs, cols)):
+            raise RfxError("collect: one result of its column's dtype per column")
+        rows_out = self.empty(m) if want_rows else None
+        nc = len(cols)
+        self._xcheck(self.lib.rfx_exec_group_collect(self._x, C.byref(part), rows.data_ptr() if rows is not None and m else None, n,
+                                                     (C.c_void_p * max(1, nc))(*[c.data_ptr() for c in cols]), (C.c_int32 * max(1, nc))(*[c.element_size() for c in cols]),
+                                                     nc, (C.c_void_p * max(1, nc))(*[o.data_ptr() for o in outs]), int(want_rows),
+                                                     rows_out.data_ptr() if want_rows and m else None), "collect")
+        self.sync()
+        return self._view(own, part.d_offsets, int(groups) + 1, torch.int64), outs, rows_out
+
+    def _group_members(self, key, columns, where, table, want_rows: bool):
+        if self.shards > 1:  # (the planner's own refusal, before anything else runs)
+            self._xcheck(self.lib.rfx_exec_group_partition(self._x, None, 0, 0, C.byref(L.Partition())), "partition")
+        from . import joins
+        k = self._check_col(self._resolve(key, table))
+        if k.dtype != torch.int64:
+            raise RfxError("group key must be i64 on this path")
+        n = k.numel()
+        names = list(columns)
+        cols = [self._resolve(columns[c] if isinstance(columns, dict) else c, table) for c in names]
+        cols = [self._check_col(c.view(torch.int8) if c.dtype == torch.bool else c, n) for c in cols]
+        if any(c.dtype not in self._COLLECT_DTYPES for c in cols):
+            raise RfxError("collect: columns are tensors of int8 (bool), uint8, int16, int32, int64 or float64")
+        rows = self.where(where, table) if where is not None else None
+        m = rows.numel() if rows is not None else n
+        if m == 0:
+            keys, gid = self.empty(0), self.empty(0)
+        else:  # the groups in first-occurrence order, then every selected row's place among them: its key looked up in the groups' keys
+            keys = self.group_by(key, [], where, table)["keys"]
+            gid = joins.join_index(self, ["k"], {"k": self.at_ids(k, rows) if rows is not None else k}, {"k": keys})
+        part, own = self._partition(gid, keys.numel())
+        outs = [self.empty(m, c.dtype) for c in cols]
+        rows_out = self.empty(m) if want_rows else None
+        nc = len(cols)
+        self._xcheck(self.lib.rfx_exec_group_collect(self._x, C.byref(part), rows.data_ptr() if rows is not None and m else None, n,
+                                                     (C.c_void_p * max(1, nc))(*[c.data_ptr() for c in cols]), (C.c_int32 * max(1, nc))(*[c.element_size() for c in cols]),
+                                                     nc, (C.c_void_p * max(1, nc))(*[o.data_ptr() for o in outs]), int(want_rows),
+                                                     rows_out.data_ptr() if want_rows and m else None), "collect")
+        self.sync()  # (the partition's blocks go back to the pool with `own`: nothing may still read them)
+        return keys, self._view(own, part.d_offsets, keys.numel() + 1, torch.int64), dict(zip(names, outs)), rows_out
+
+    def group_rows(self, key, where=None, table=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``select {r: (row c) by: key from: t [where: p]}`` in its device-resident form -> (keys, offsets, rows): the groups' keys in first-occurrence
+        order, and group g's row numbers, ascending, at ``rows[offsets[g]:offsets[g + 1]]`` (aggr_row, core/aggr.c:3118-3136).  One shard.  (syncs)"""
+        keys, offsets, _, rows = self._group_members(key, {}, where, table, True)
+        return keys, offsets, rows
+
+    def group_collect(self, key, columns, where=None, table=None):
+        """``select {c: c ... by: key from: t [where: p]}``: every group's cells -> (keys, offsets, {name: cells}); ``columns`` a dict name -> device
+        column, or a list of ``table``'s names; group g's cells of a column, in row order, at ``cells[offsets[g]:offsets[g + 1]]``, in the column's own
+        dtype (aggr_collect, core/aggr.c:3021-3116).  Any number of columns: eight to a launch over one partition.  One shard.  (syncs)"""
+        if not columns:
+            raise RfxError("collect: at least one column")
+        keys, offsets, cells, _ = self._group_members(key, columns, where, table, False)
+        return keys, offsets, cells
+
     def eval_expr(self, expr, table=None) -> torch.Tensor:
         """``(op x y)`` / an expression tree over columns and atoms as a device column: ray_add .. ray_mod (binop_map,
         core/math.c:2280-2345) in ONE pass whatever the depth."""

@@ -69,6 +69,9 @@ OPS_PROTOTYPES = {
     "rfx_upsert": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
     "rfx_insert": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int64]),
     "rfx_last_upsert_on_gpu": (C.c_int, []),
+    "rfx_row": (C.c_void_p, [C.c_void_p]),
+    "rfx_collect": (C.c_void_p, [C.c_void_p]),
+    "rfx_last_collect_on_gpu": (C.c_int, []),
     "rfx_cache_clear": (None, []),
     "rfx_cache_bytes": (C.c_int64, []),
     "rfx_last_select_on_gpu": (C.c_int, []),
@@ -121,6 +124,55 @@ def vector(a: np.ndarray) -> int:
     if a.size:
         C.memmove(payload(o), a.ctypes.data, a.nbytes)
     return o
+
+
+T_U8, T_I16, T_I32, T_DATE, T_TIME, T_TIMESTAMP, T_MAPFILTER, T_MAPGROUP, T_NULL = 2, 3, 4, 7, 8, 9, 71, 72, 126
+TYPE_NAMES = {"b8": T_B8, "u8": T_U8, "i16": T_I16, "i32": T_I32, "i64": T_I64, "symbol": T_SYMBOL, "date": T_DATE, "time": T_TIME, "timestamp": T_TIMESTAMP,
+              "f64": T_F64}
+
+
+def typed_vector(a: np.ndarray, t) -> int:
+    """A vector of the reference's type code `t` (or its name in TYPE_NAMES) over the cells of `a`, whose dtype must be that type's cell: the narrow
+    types (U8, I16, I32 / DATE / TIME) and the 8-byte ones that share int64 cells (SYMBOL, TIMESTAMP)."""
+    t = TYPE_NAMES[t] if isinstance(t, str) else int(t)
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.bool_:
+        a = a.astype(np.int8)
+    if np.dtype(NP_OF[t]) != a.dtype:
+        raise TypeError(f"type {t} holds {np.dtype(NP_OF[t])} cells, not {a.dtype}")
+    o = lib().rfx_host_vector(t, a.size)
+    if a.size:
+        C.memmove(payload(o), a.ctypes.data, a.nbytes)
+    return o
+
+
+def group_index(itype: int, groups: int, group_ids: np.ndarray, shift=None, source=None, filt=None, firsts=None) -> int:
+    """The reference's 7-slot group index (index_group_build): [type, groups, ids | key table, shift, source column, filter ids, first rows]; slots that
+    are not given stay the null object."""
+    ix = lib().rfx_host_list(7)
+    arr = (C.c_void_p * 7).from_address(payload(ix))
+    arr[0], arr[1] = atom(int(itype)), atom(int(groups))
+    arr[2] = vector(np.asarray(group_ids, dtype=np.int64))
+    arr[3] = atom(int(shift) if itype == 1 else -(2 ** 63))
+    if source is not None:
+        arr[4] = vector(np.asarray(source, dtype=np.int64))
+    if filt is not None:
+        arr[5] = vector(np.asarray(filt, dtype=np.int64))
+    if firsts is not None:
+        arr[6] = vector(np.asarray(firsts, dtype=np.int64))
+    return ix
+
+
+def pair(val: int, index: int, t: int = T_MAPGROUP) -> int:
+    """A lazy (val, index) pair as an FN_AGGR built-in receives it: MAPGROUP (a group index) or MAPFILTER (row ids)."""
+    p = list_of([val, index])
+    header(p).type = t
+    return p
+
+
+def list_to_numpy(o: int):
+    """A LIST of vectors -> [(type code, attribute byte, cells)] per item"""
+    return [(header(i).type, header(i).attrs, to_numpy(i)) for i in list_items(o)]
 
 
 def to_numpy(o: int) -> np.ndarray:
