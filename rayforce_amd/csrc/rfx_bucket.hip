@@ -2,15 +2,14 @@
 // floor / ceil / round (core/math.c:2047-2117), neg (ray_neg, core/order.c:445-497), within (ray_within, core/items.c:848-872).
 // Streaming and scatter kernels: a lane owns four consecutive cells per step (16-byte loads and stores at either element width), no LDS.
 // The cell rules live in rfx_common.hpp (rfx_xbar_*, rfx_floor_f64_bits ...): the by: path buckets its keys with the same functions.
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef u64 v2q __attribute__((ext_vector_type(2)));
 
 // four consecutive cells from row r (a multiple of 4) as raw bits; 4-byte cells sign-extended
 __device__ __forceinline__ void bk_ld4(const void *p, bool wide, i64 r, u64 v[4]) {
     if (wide) {
-        const v2q a = __builtin_nontemporal_load((const v2q *)((const u64 *)p + r)), b = __builtin_nontemporal_load((const v2q *)((const u64 *)p + r + 2));
+        const rfx_v2q a = __builtin_nontemporal_load((const rfx_v2q *)((const u64 *)p + r)), b = __builtin_nontemporal_load((const rfx_v2q *)((const u64 *)p + r + 2));
         v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
     } else {
         const v4u a = __builtin_nontemporal_load((const v4u *)((const unsigned *)p + r));
@@ -20,10 +19,10 @@ __device__ __forceinline__ void bk_ld4(const void *p, bool wide, i64 r, u64 v[4]
 __device__ __forceinline__ u64 bk_ld1(const void *p, bool wide, i64 r) { return wide ? ((const u64 *)p)[r] : (u64)(i64)((const int *)p)[r]; }
 __device__ __forceinline__ void bk_st4(void *p, bool wide, i64 r, const u64 v[4]) {
     if (wide) {
-        v2q a, b;
+        rfx_v2q a, b;
         a.x = v[0]; a.y = v[1]; b.x = v[2]; b.y = v[3];
-        __builtin_nontemporal_store(a, (v2q *)((u64 *)p + r));
-        __builtin_nontemporal_store(b, (v2q *)((u64 *)p + r + 2));
+        __builtin_nontemporal_store(a, (rfx_v2q *)((u64 *)p + r));
+        __builtin_nontemporal_store(b, (rfx_v2q *)((u64 *)p + r + 2));
     } else {
         v4u a;
         a.x = (unsigned)v[0]; a.y = (unsigned)v[1]; a.z = (unsigned)v[2]; a.w = (unsigned)v[3];

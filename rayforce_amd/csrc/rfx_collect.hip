@@ -10,13 +10,10 @@
 //                  the sources of its 2048 cells in LDS (perm by 16-byte loads, rows through it), then every column gathers its cells in its own width
 //                  and leaves them in whole 16-byte stores -- the groups of cells are cut at the OUTPUT's 16-byte boundaries, so a base that is only
 //                  cell-aligned costs single-cell stores at the two ends of the column and nowhere else.  A column without cells is the identity (`row`).
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 
 #define COL_STEPS 8
 #define COL_TILE (RFX_BLOCK * COL_STEPS) /* cells per workgroup: 2048 (16 KB of staged sources) */
-
-typedef u64 col_v2q __attribute__((ext_vector_type(2)));
-void rfx_plane_invalidate(rfx_ctx *c); // rfx_group_plane.hip
 
 // ---- how many ids lie outside [0, bound): per-wave ballots, one integer add per workgroup ----
 __global__ __launch_bounds__(RFX_BLOCK) void k_col_check(const i64 *__restrict__ ids, i64 m, i64 bound, unsigned long long *__restrict__ bad) {
@@ -57,16 +54,7 @@ struct col_cols {
 template <int WID> __device__ __forceinline__ u64 col_get(const unsigned char *__restrict__ in, i64 s) {
     if (s < 0) return 0ULL;
     if (!in) return (u64)s;
-    if (WID == 8) return ((const u64 *)in)[s];
-    if (WID == 4) return ((const unsigned *)in)[s];
-    if (WID == 2) return ((const unsigned short *)in)[s];
-    return in[s];
-}
-template <int WID> __device__ __forceinline__ void col_put(unsigned char *__restrict__ out, i64 j, u64 v) {
-    if (WID == 8) ((u64 *)out)[j] = v;
-    else if (WID == 4) ((unsigned *)out)[j] = (unsigned)v;
-    else if (WID == 2) ((unsigned short *)out)[j] = (unsigned short)v;
-    else out[j] = (unsigned char)v;
+    return rfx_cell_get<WID>(in, s);
 }
 // one column over the workgroup's tile [base, base + COL_TILE): the cells in groups of R = 16 / WID that start at the output's 16-byte boundaries -- group k
 // holds the cells [base - a + k R, + R), a = the cells between the boundary below the output's base and the base.  A whole group inside the tile and the
@@ -87,13 +75,13 @@ __device__ __forceinline__ void col_gather_col(const unsigned char *__restrict__
                 if (WID == 8) w[i] = v;
                 else w[(i * WID) / 8] |= v << (((i * WID) & 7) * 8);
             }
-            col_v2q o;
+            rfx_v2q o;
             o.x = w[0]; o.y = w[1];
-            *(col_v2q *)(out + j0 * WID) = o;
+            *(rfx_v2q *)(out + j0 * WID) = o;
         } else {
             for (int i = 0; i < R; i++) {
                 const i64 j = j0 + i;
-                if (j >= base && j < end) col_put<WID>(out, j, col_get<WID>(in, sl[j - base]));
+                if (j >= base && j < end) rfx_cell_put<WID>(out, j, col_get<WID>(in, sl[j - base]));
             }
         }
     }
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_col_gather(const col_cols C, cons
         const i64 j0 = base + (i64)g * 2;
         i64 s0 = -1, s1 = -1;
         if (j0 + 2 <= m) {
-            const col_v2q v = *(const col_v2q *)(perm + j0);
+            const rfx_v2q v = *(const rfx_v2q *)(perm + j0);
             s0 = (i64)v.x;
             s1 = (i64)v.y;
         } else if (j0 < m) s0 = perm[j0];
@@ -127,14 +115,6 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_col_gather(const col_cols C, cons
     }
 }
 
-static int col_stream_grid(rfx_ctx *c, i64 threads) {
-    i64 blocks = (threads + RFX_BLOCK - 1) / RFX_BLOCK;
-    int grid = rfx_grid(c) * 4;
-    if (blocks < 1) blocks = 1;
-    if (blocks < grid) grid = (int)blocks;
-    return grid;
-}
-
 extern "C" int rfx_hip_ids_check(rfx_ctx_t *ctx, const int64_t *d_ids, int64_t m, int64_t bound, int64_t *bad) {
     rfx_ctx *c = (rfx_ctx *)ctx;
     RFX_REQUIRE(c && bad, RFX_EINVAL, "NULL argument");
@@ -153,7 +133,7 @@ extern "C" int rfx_hip_ids_check(rfx_ctx_t *ctx, const int64_t *d_ids, int64_t m
     hipError_t e = hipMemsetAsync(d_bad, 0, 8, c->stream);
     RFX_KERNEL_BEGIN(c);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_col_check, dim3(col_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_ids, (i64)m, (i64)bound, (unsigned long long *)d_bad);
+        hipLaunchKernelGGL(k_col_check, dim3(rfx_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_ids, (i64)m, (i64)bound, (unsigned long long *)d_bad);
         e = hipGetLastError();
     }
     RFX_KERNEL_END(c);
@@ -188,7 +168,7 @@ extern "C" int rfx_hip_group_partition(rfx_ctx_t *ctx, const int64_t *d_gid, int
         return rc;
     }
     RFX_KERNEL_BEGIN(c);
-    hipLaunchKernelGGL(k_col_offsets, dim3(col_stream_grid(c, m + 1)), dim3(RFX_BLOCK), 0, c->stream, (const int *)d_sorted, (i64)m, (i64)groups, (i64 *)d_offsets);
+    hipLaunchKernelGGL(k_col_offsets, dim3(rfx_stream_grid(c, m + 1)), dim3(RFX_BLOCK), 0, c->stream, (const int *)d_sorted, (i64)m, (i64)groups, (i64 *)d_offsets);
     RFX_KERNEL_END(c);
     hipError_t e = hipGetLastError();
     const hipError_t es = hipStreamSynchronize(c->stream);
@@ -212,7 +192,7 @@ extern "C" int rfx_hip_group_collect(rfx_ctx_t *ctx, const rfx_collect_col_t *co
     memset(&C, 0, sizeof(C));
     for (int k = 0; k < ncols; k++) {
         const int w = cols[k].width;
-        RFX_REQUIRE(w == 1 || w == 2 || w == 4 || w == 8, RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
+        RFX_REQUIRE(rfx_width_ok(w), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
         RFX_REQUIRE(cols[k].d_col || w == 8, RFX_EINVAL, "the identity column has 8-byte cells");
         RFX_REQUIRE(((uintptr_t)cols[k].d_col & (uintptr_t)(w - 1)) == 0, RFX_EINVAL, "a column that is not cell-aligned");
         RFX_REQUIRE(cols[k].d_out && ((uintptr_t)cols[k].d_out & (uintptr_t)(w - 1)) == 0, RFX_EINVAL, "NULL result, or one that is not cell-aligned");
@@ -221,12 +201,7 @@ extern "C" int rfx_hip_group_collect(rfx_ctx_t *ctx, const rfx_collect_col_t *co
         C.width[k] = w;
     }
     C.ncols = ncols;
-    // the outputs change under whatever a scope pass left partitioned or sampled, as after an upload (rfx_hip_upsert_place)
-    c->ck_valid = 0;
-    c->pc_valid = 0;
-    rfx_plane_invalidate(c);
-    if (c->ext_p[5]) memset(c->ext_p[5], 0, 256);
-    if (c->ext_p[6]) memset(c->ext_p[6], 0, 256);
+    rfx_ctx_device_written(c);
     const i64 nblk = (m + COL_TILE - 1) / COL_TILE; // < 2^20
     RFX_KERNEL_BEGIN(c);
     hipLaunchKernelGGL(k_col_gather, dim3((unsigned)nblk), dim3(RFX_BLOCK), 0, c->stream, C, (const i64 *)d_perm, (const i64 *)d_rows, (i64)m, (i64)col_len);

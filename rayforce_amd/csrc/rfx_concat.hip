@@ -9,13 +9,10 @@
 //                    else -- the first and last accesses of a span, an access that crosses spans, the output's tail -- byte by byte, every byte from
 //                    its own span, stored as the whole access when all 16 bytes are the output's, byte by byte at the tail.  Nothing is read outside
 //                    a span or written outside the output.
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 
 #define CC_UNROLL 4                           /* 16-byte accesses per thread */
 #define CC_TILE (RFX_BLOCK * 16 * CC_UNROLL)  /* bytes of output per workgroup: 16 KB */
-
-typedef u64 cc_v2q __attribute__((ext_vector_type(2)));
-void rfx_plane_invalidate(rfx_ctx *c); // rfx_group_plane.hip
 
 struct cc_col {
     const i64 *pref;          // S + 1 ascending byte offsets, pref[0] = 0, pref[S] = total
@@ -59,19 +56,19 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_concat_spans(const cc_col *__rest
             const u64 a = src[s] + (u64)(b - p0);
             const u64 k16 = a & 15;
             if (k16 == 0) {
-                __builtin_nontemporal_store(__builtin_nontemporal_load((const cc_v2q *)a), (cc_v2q *)(out + b));
+                __builtin_nontemporal_store(__builtin_nontemporal_load((const rfx_v2q *)a), (rfx_v2q *)(out + b));
                 continue;
             }
             const u64 a0 = a - k16;
             if (a0 >= src[s] && a0 + 32 <= src[s] + (u64)(p1 - p0)) { // both aligned words are the span's own
-                const cc_v2q lo = __builtin_nontemporal_load((const cc_v2q *)a0), hi = __builtin_nontemporal_load((const cc_v2q *)(a0 + 16));
+                const rfx_v2q lo = __builtin_nontemporal_load((const rfx_v2q *)a0), hi = __builtin_nontemporal_load((const rfx_v2q *)(a0 + 16));
                 const bool up = k16 >= 8;
                 const u64 w0 = up ? lo.y : lo.x, w1 = up ? hi.x : lo.y, w2 = up ? hi.y : hi.x;
                 const unsigned sh = (unsigned)(k16 & 7) * 8;
-                cc_v2q o;
+                rfx_v2q o;
                 o.x = sh ? (w0 >> sh) | (w1 << (64 - sh)) : w0;
                 o.y = sh ? (w1 >> sh) | (w2 << (64 - sh)) : w1;
-                __builtin_nontemporal_store(o, (cc_v2q *)(out + b));
+                __builtin_nontemporal_store(o, (rfx_v2q *)(out + b));
                 continue;
             }
         }
@@ -93,16 +90,14 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_concat_spans(const cc_col *__rest
             else hi |= v << (8 * (j - 8));
         }
         if (whole) {
-            cc_v2q o;
+            rfx_v2q o;
             o.x = lo; o.y = hi;
-            *(cc_v2q *)(out + b) = o;
+            *(rfx_v2q *)(out + b) = o;
         } else {
             for (int j = 0; j < nb; j++) out[b + j] = (unsigned char)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))) & 0xFF);
         }
     }
 }
-
-static bool cc_width_ok(int w) { return w == 1 || w == 2 || w == 4 || w == 8; }
 
 extern "C" int rfx_hip_concat_cols(rfx_ctx_t *c, const rfx_concat_col_t *cols, int ncols) {
     RFX_REQUIRE(c && cols, RFX_EINVAL, "NULL argument");
@@ -112,7 +107,7 @@ extern "C" int rfx_hip_concat_cols(rfx_ctx_t *c, const rfx_concat_col_t *cols, i
     int live = 0;
     for (int k = 0; k < ncols; k++) {
         const rfx_concat_col_t *col = &cols[k];
-        RFX_REQUIRE(cc_width_ok(col->width), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
+        RFX_REQUIRE(rfx_width_ok(col->width), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
         RFX_REQUIRE(col->nspans >= 0 && (col->nspans == 0 || col->spans), RFX_EINVAL, "NULL span list");
         i64 s_live = 0, atoms = 0, cells = 0;
         for (i64 s = 0; s < col->nspans; s++) {
@@ -183,12 +178,7 @@ extern "C" int rfx_hip_concat_cols(rfx_ctx_t *c, const rfx_concat_col_t *cols, i
         rfx_hip_free(c, d_tab);
         RFX_REQUIRE(0, RFX_ELIMIT, "more output tiles than one grid holds");
     }
-    // the outputs change under whatever a scope pass left partitioned or sampled (matched by addresses and sizes alone), as after an upload
-    c->ck_valid = 0;
-    c->pc_valid = 0;
-    rfx_plane_invalidate(c);
-    if (c->ext_p[5]) memset(c->ext_p[5], 0, 256);
-    if (c->ext_p[6]) memset(c->ext_p[6], 0, 256);
+    rfx_ctx_device_written(c);
     hipError_t e = hipMemcpyAsync(d_tab, h, bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (the table has left the host block)
     free(h);

@@ -1,6 +1,6 @@
 // rfx_ctx.hip -- context, device memory, timers, synthetic-column generator, plan builder.
 #include <pthread.h>
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -527,16 +527,21 @@ extern "C" int rfx_hip_free(rfx_ctx_t *c, void *d_ptr) {
     pthread_mutex_unlock(&g_pool_mu);
     return rc;
 }
-extern "C" int rfx_hip_h2d(rfx_ctx_t *c, void *d_dst, const void *src, size_t bytes) {
-    RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
-    if (!bytes) return RFX_OK;
-    // device data changed under whatever a scope pass left partitioned (the residency cache refreshes stale columns IN PLACE, at the same
-    // device address): partitions are matched by pointers and sizes only, so none survives an upload
+// Device data changes under whatever a scope pass left partitioned (an upload refreshes a stale column IN PLACE, at the same device address; a
+// verb's result takes a block the pool handed out before): partitions, planes and memos are matched by pointers and sizes only, so none
+// survives a write -- the chunk and partition states, the planes, and the remembered sample (rfx_chunk_scope) and `where` estimate, which only
+// size and route, but why keep them.  EVERY path that writes device memory calls this before it does.
+void rfx_ctx_device_written(rfx_ctx *c) {
     c->ck_valid = 0;
     c->pc_valid = 0;
     rfx_plane_invalidate(c);
-    if (c->ext_p[5]) memset(c->ext_p[5], 0, 256); // ... nor does a remembered sample (rfx_chunk_scope; it only sizes and routes, but why keep it)
-    if (c->ext_p[6]) memset(c->ext_p[6], 0, 256); // ... or a remembered `where` estimate
+    if (c->ext_p[5]) memset(c->ext_p[5], 0, 256);
+    if (c->ext_p[6]) memset(c->ext_p[6], 0, 256);
+}
+extern "C" int rfx_hip_h2d(rfx_ctx_t *c, void *d_dst, const void *src, size_t bytes) {
+    RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
+    if (!bytes) return RFX_OK;
+    rfx_ctx_device_written(c);
     RFX_HIP_CHECK(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     RFX_HIP_CHECK(hipStreamSynchronize(c->stream));
     return RFX_OK;
@@ -557,11 +562,7 @@ extern "C" int rfx_hip_d2h_async(rfx_ctx_t *c, void *dst, const void *d_src, siz
 extern "C" int rfx_hip_memset(rfx_ctx_t *c, void *d_dst, int byte, size_t bytes) {
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
     if (!bytes) return RFX_OK;
-    c->ck_valid = 0;
-    c->pc_valid = 0;
-    rfx_plane_invalidate(c);
-    if (c->ext_p[5]) memset(c->ext_p[5], 0, 256);
-    if (c->ext_p[6]) memset(c->ext_p[6], 0, 256);
+    rfx_ctx_device_written(c);
     RFX_HIP_CHECK(hipMemsetAsync(d_dst, byte, bytes, c->stream));
     return RFX_OK;
 }

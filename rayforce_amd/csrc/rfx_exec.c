@@ -76,6 +76,20 @@ static inline int64_t now_ns(void) {
 }
 #define T_BEGIN(x) const int64_t t0_ = (x)->timing ? now_ns() : 0
 #define T_END(x, which) do { if ((x)->timing) (x)->stat[which] += now_ns() - t0_; } while (0)
+/* a verb that reads or writes across whole columns: one shard, one rank, on the calling thread */
+static int exec_one_shard(rfx_exec_t *x, const char *what) {
+    x->err[0] = 0;
+    if (x->nshards > 1 || x->has_tr) {
+        snprintf(x->err, sizeof(x->err), "rfx_exec: %s over a sharded table", what);
+        return RFX_ELIMIT;
+    }
+    rfx_hip_ctx_bind_thread(x->ctx[0]);
+    return RFX_OK;
+}
+static int exec_fail(rfx_exec_t *x, const char *verb, const char *step, int rc) {
+    if (rc != RFX_OK) snprintf(x->err, sizeof(x->err), "rfx_exec: %s %s: %s", verb, step, rfx_hip_last_error());
+    return rc;
+}
 
 /* The planner by concern (round 6: one 2 150-line file before).  ONE translation unit, read in this order: */
 #include "rfx_exec_threads.c"

@@ -3,23 +3,14 @@
  * (index_asof_join_obj, core/index.c:3194-3267) and searches that list by time.  Here the lists are ONE permutation of the right rows -- a stable
  * sort by "first row of my group" -- with the groups' boundaries and the times laid out in that order; the kernels of rfx_asof.hip do the rest.
  * One shard. */
-static int asof_one_shard(rfx_exec_t *x, const char *what) {
-    if (x->nshards > 1 || x->has_tr) {
-        snprintf(x->err, sizeof(x->err), "rfx_exec: %s over a sharded table", what);
-        return RFX_ELIMIT;
-    }
-    return RFX_OK;
-}
 int rfx_exec_asof_index(rfx_exec_t *x, const void *const *dlk, const void *const *drk, int nk, const int64_t *d_lt, const int64_t *d_rt, int64_t nl,
                         int64_t nr, int64_t *d_ids, int *collision) {
     if (collision) *collision = 0;
     if (!x || !dlk || !drk || nk < 1 || nk > RFX_MAX_KEYS || nl < 0 || nr < 0 || (nl > 0 && (!d_ids || !d_lt)) || (nr > 0 && !d_rt)) return RFX_EINVAL;
-    x->err[0] = 0;
-    int rc = asof_one_shard(x, "asof join");
+    int rc = exec_one_shard(x, "asof join");
     if (rc != RFX_OK) return rc;
     if (nl == 0) return RFX_OK; /* (nothing to answer: no launch) */
     rfx_ctx_t *c = x->ctx[0];
-    rfx_hip_ctx_bind_thread(c);
     if (nr == 0) { /* no right row: no group for anybody */
         if ((rc = rfx_hip_fill_i64(c, d_ids, nl, NULL_I64)) != RFX_OK) snprintf(x->err, sizeof(x->err), "rfx_exec: asof: %s", rfx_hip_last_error());
         else x->stat[RFX_XSTAT_ASOF_JOINS]++;
@@ -66,11 +57,9 @@ out:
 }
 int rfx_exec_bin(rfx_exec_t *x, const int64_t *d_x, int64_t nx, const int64_t *d_y, int64_t ny, int right, int64_t *d_out) {
     if (!x || nx < 0 || ny < 0 || (nx > 0 && !d_x) || (ny > 0 && (!d_y || !d_out))) return RFX_EINVAL;
-    x->err[0] = 0;
-    int rc = asof_one_shard(x, "bin");
+    int rc = exec_one_shard(x, "bin");
     if (rc != RFX_OK) return rc;
     if (ny == 0) return RFX_OK;
-    rfx_hip_ctx_bind_thread(x->ctx[0]);
     rc = rfx_hip_seg_search(x->ctx[0], d_y, ny, NULL, 0, NULL, nx, d_x, NULL, right != 0, right ? nx : -1, d_out);
     if (rc != RFX_OK) {
         snprintf(x->err, sizeof(x->err), "rfx_exec: bin: %s", rfx_hip_last_error());

@@ -101,18 +101,9 @@ void rfx_exec_rows_free(rfx_exec_t *x, rfx_rows_t *r) {
     memset(r, 0, sizeof(*r));
 }
 
-static int rows_one_shard(rfx_exec_t *x, const char *verb) {
-    x->err[0] = 0;
-    if (x->nshards > 1 || x->has_tr) {
-        snprintf(x->err, sizeof(x->err), "rfx_exec: %s over a sharded table", verb);
-        return RFX_ELIMIT;
-    }
-    rfx_hip_ctx_bind_thread(x->ctx[0]);
-    return RFX_OK;
-}
 int rfx_exec_take(rfx_exec_t *x, const void *const *d_cols, const int32_t *kinds, int ncols, int64_t l, int64_t j0, int64_t m, void *const *d_outs) {
     if (!x || !d_cols || !kinds || !d_outs || ncols < 1 || l < 0 || m < 0) return RFX_EINVAL;
-    int rc = rows_one_shard(x, "take");
+    int rc = exec_one_shard(x, "take");
     for (int k = 0; k < ncols && rc == RFX_OK; k++)
         if ((rc = rfx_hip_rows_take(x->ctx[0], d_cols[k], kinds[k], l, j0, m, d_outs[k])) != RFX_OK) snprintf(x->err, sizeof(x->err), "rfx_exec: take: %s", rfx_hip_last_error());
     if (rc == RFX_OK) {
@@ -124,7 +115,7 @@ int rfx_exec_take(rfx_exec_t *x, const void *const *d_cols, const int32_t *kinds
 }
 int rfx_exec_take_atom(rfx_exec_t *x, int32_t kind, uint64_t bits, int64_t m, void *d_out) {
     if (!x || m < 0) return RFX_EINVAL;
-    int rc = rows_one_shard(x, "take");
+    int rc = exec_one_shard(x, "take");
     if (rc == RFX_OK && (rc = rfx_hip_rows_fill(x->ctx[0], kind, bits, m, d_out)) != RFX_OK) snprintf(x->err, sizeof(x->err), "rfx_exec: take: %s", rfx_hip_last_error());
     if (rc == RFX_OK) {
         x->stat[RFX_XSTAT_ROWS_TAKES]++;
@@ -135,7 +126,7 @@ int rfx_exec_take_atom(rfx_exec_t *x, int32_t kind, uint64_t bits, int64_t m, vo
 }
 int rfx_exec_reverse(rfx_exec_t *x, const void *d_col, int32_t kind, int64_t l, void *d_out) {
     if (!x || l < 0) return RFX_EINVAL;
-    int rc = rows_one_shard(x, "reverse");
+    int rc = exec_one_shard(x, "reverse");
     if (rc == RFX_OK && (rc = rfx_hip_rows_reverse(x->ctx[0], d_col, kind, l, d_out)) != RFX_OK) snprintf(x->err, sizeof(x->err), "rfx_exec: reverse: %s", rfx_hip_last_error());
     if (rc == RFX_OK) {
         x->stat[RFX_XSTAT_ROWS_REVERSES]++;

@@ -8,17 +8,9 @@ static int sort_type_ok(int32_t t) {
     return t == RFX_I64 || t == RFX_F64 || t == RFX_I32 || t == RFX_I32_WIDE || t == RFX_I16 || t == RFX_U8 || t == RFX_B8;
 }
 #define SORT_TYPES_WHY "rfx_exec: sort keys are i64 / timestamp / f64 columns, or i32 / date / time (raw or widened), i16, u8 and b8 ones on one shard"
-static int sort_one_shard(rfx_exec_t *x) {
-    if (x->nshards > 1 || x->has_tr) {
-        snprintf(x->err, sizeof(x->err), "rfx_exec: sort over a sharded table");
-        return RFX_ELIMIT;
-    }
-    return RFX_OK;
-}
 int rfx_exec_sort(rfx_exec_t *x, const void *const *d_cols, const int32_t *types, int ncols, int descending, int64_t n, int64_t *d_perm) {
     if (!x || !d_cols || !types || ncols < 1 || n < 0 || (n > 0 && !d_perm)) return RFX_EINVAL;
-    x->err[0] = 0;
-    int rc = sort_one_shard(x);
+    int rc = exec_one_shard(x, "sort");
     if (rc != RFX_OK) return rc;
     for (int k = 0; k < ncols; k++)
         if (!sort_type_ok(types[k]) || (n > 0 && !d_cols[k])) {
@@ -27,7 +19,6 @@ int rfx_exec_sort(rfx_exec_t *x, const void *const *d_cols, const int32_t *types
         }
     if (n == 0) return RFX_OK;
     rfx_ctx_t *c = x->ctx[0];
-    rfx_hip_ctx_bind_thread(c);
     /* the least significant column first; every level reads the running permutation and writes the next one (never in place) */
     void *other = NULL;
     if (ncols > 1 && (rc = rfx_hip_malloc(c, &other, (size_t)n * 8)) != RFX_OK) {
@@ -54,8 +45,7 @@ int rfx_exec_sort(rfx_exec_t *x, const void *const *d_cols, const int32_t *types
 }
 int rfx_exec_sort_values(rfx_exec_t *x, const void *d_col, int32_t type, int descending, int64_t n, void *d_out, int64_t *d_perm) {
     if (!x || n < 0 || (n > 0 && (!d_col || !d_out))) return RFX_EINVAL;
-    x->err[0] = 0;
-    int rc = sort_one_shard(x);
+    int rc = exec_one_shard(x, "sort");
     if (rc != RFX_OK) return rc;
     if (!sort_type_ok(type)) {
         snprintf(x->err, sizeof(x->err), SORT_TYPES_WHY);
@@ -63,7 +53,6 @@ int rfx_exec_sort_values(rfx_exec_t *x, const void *d_col, int32_t type, int des
     }
     if (n == 0) return RFX_OK;
     int32_t passes = 0;
-    rfx_hip_ctx_bind_thread(x->ctx[0]);
     rc = rfx_hip_sort_values(x->ctx[0], d_col, type, n, descending, d_out, d_perm, &passes);
     x->stat[RFX_XSTAT_SORTS]++;
     x->stat[RFX_XSTAT_SORT_PASSES] += passes;

@@ -1,28 +1,15 @@
 /* rfx_exec_upsert.c -- part of the planner's ONE translation unit (rfx_exec.c #includes it -- the Makefile does not compile it on its own).
  * upsert and insert (rfx_upsert.hip): index, plan, then per column copy + fill + place.  The index reads across whole columns and the place writes
  * anywhere in them, so these run on one shard, one rank, as concat does. */
-static int upsert_one_shard(rfx_exec_t *x) {
-    x->err[0] = 0;
-    if (x->nshards > 1 || x->has_tr) {
-        snprintf(x->err, sizeof(x->err), "rfx_exec: upsert over a sharded table");
-        return RFX_ELIMIT;
-    }
-    rfx_hip_ctx_bind_thread(x->ctx[0]);
-    return RFX_OK;
-}
-static int upsert_fail(rfx_exec_t *x, const char *step, int rc) {
-    if (rc != RFX_OK) snprintf(x->err, sizeof(x->err), "rfx_exec: upsert %s: %s", step, rfx_hip_last_error());
-    return rc;
-}
 int rfx_exec_upsert_index(rfx_exec_t *x, const void *const *d_table_keys, const void *const *d_batch_keys, int nkeys, int64_t n, int64_t m, int64_t *d_idx,
                           int *undefined) {
     if (undefined) *undefined = 0;
     if (!x || !d_table_keys || !d_batch_keys || nkeys < 1 || nkeys > RFX_MAX_KEYS || n < 0 || m < 0 || (m > 0 && !d_idx)) return RFX_EINVAL;
-    int rc = upsert_one_shard(x);
+    int rc = exec_one_shard(x, "upsert");
     if (rc != RFX_OK || m == 0) return rc;
     rfx_ctx_t *c = x->ctx[0];
     const int64_t t0 = now_ns();
-    if (n == 0) rc = upsert_fail(x, "index", rfx_hip_fill_i64(c, d_idx, m, INT64_MIN)); /* (a table of no rows: all nulls without a lookup) */
+    if (n == 0) rc = exec_fail(x, "upsert", "index", rfx_hip_fill_i64(c, d_idx, m, INT64_MIN)); /* (a table of no rows: all nulls without a lookup) */
     else if (nkeys == 1) {
         int route = RFX_SET_ROUTE_NONE;
         rc = rfx_exec_member(x, (const int64_t *)d_table_keys[0], n, (const int64_t *)d_batch_keys[0], m, 1, d_idx, &route);
@@ -32,23 +19,23 @@ int rfx_exec_upsert_index(rfx_exec_t *x, const void *const *d_table_keys, const 
         rc = rfx_exec_join_index(x, d_batch_keys, d_table_keys, nkeys, m, n, d_idx, &collision);
         if (rc == RFX_ESTATE && collision && undefined) *undefined = 2;
     }
-    if (rc == RFX_OK) rc = upsert_fail(x, "index", rfx_hip_ctx_sync(c));
+    if (rc == RFX_OK) rc = exec_fail(x, "upsert", "index", rfx_hip_ctx_sync(c));
     x->stat[RFX_XSTAT_NS_UPSERT_INDEX] += now_ns() - t0;
     return rc;
 }
 int rfx_exec_upsert_plan(rfx_exec_t *x, const int64_t *d_idx, int64_t m, int64_t n, int64_t *d_dest, int64_t *appended) {
     if (!x || !appended || m < 0 || n < 0) return RFX_EINVAL;
     *appended = 0;
-    int rc = upsert_one_shard(x);
+    int rc = exec_one_shard(x, "upsert");
     if (rc != RFX_OK) return rc;
     const int64_t t0 = now_ns();
-    rc = upsert_fail(x, "plan", rfx_hip_upsert_plan(x->ctx[0], d_idx, m, n, d_dest, appended)); /* (returns with the stream idle) */
+    rc = exec_fail(x, "upsert", "plan", rfx_hip_upsert_plan(x->ctx[0], d_idx, m, n, d_dest, appended)); /* (returns with the stream idle) */
     x->stat[RFX_XSTAT_NS_UPSERT_PLAN] += now_ns() - t0;
     return rc;
 }
 static int upsert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, const int64_t *d_dest, int64_t m, int64_t n, int64_t appended, int insert) {
     if (!x || !cols || ncols < 1 || m < 0 || n < 0 || appended < 0 || appended > m) return RFX_EINVAL;
-    int rc = upsert_one_shard(x);
+    int rc = exec_one_shard(x, "upsert");
     if (rc != RFX_OK) {
         if (insert) snprintf(x->err, sizeof(x->err), "rfx_exec: insert over a sharded table");
         return rc;
@@ -80,7 +67,7 @@ static int upsert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, 
     /* the appended cells of the columns the batch does not provide */
     for (int k = 0; k < ncols && rc == RFX_OK && appended > 0; k++)
         if (cols[k].role == RFX_UPSERT_ABSENT)
-            rc = upsert_fail(x, "fill", rfx_hip_upsert_fill(c, (char *)cols[k].d_out + (size_t)n * (size_t)cols[k].width, cols[k].width, cols[k].null_bits, appended));
+            rc = exec_fail(x, "upsert", "fill", rfx_hip_upsert_fill(c, (char *)cols[k].d_out + (size_t)n * (size_t)cols[k].width, cols[k].width, cols[k].null_bits, appended));
     /* the batch cells, RFX_MAX_COLS columns to a launch; with nothing appended the key columns have nothing to take */
     rfx_upsert_col_t pc[RFX_MAX_COLS];
     int np = 0;
@@ -93,12 +80,12 @@ static int upsert_cols(rfx_exec_t *x, const rfx_upsert_xcol_t *cols, int ncols, 
             np++;
         }
         if (np == RFX_MAX_COLS || (k == ncols - 1 && np > 0)) {
-            rc = upsert_fail(x, "place", rfx_hip_upsert_place(c, pc, np, d_dest, m, n, n + appended));
+            rc = exec_fail(x, "upsert", "place", rfx_hip_upsert_place(c, pc, np, d_dest, m, n, n + appended));
             np = 0;
         }
     }
     const int rs = rfx_hip_ctx_sync(c);
-    if (rc == RFX_OK) rc = upsert_fail(x, "place", rs);
+    if (rc == RFX_OK) rc = exec_fail(x, "upsert", "place", rs);
     x->stat[RFX_XSTAT_NS_UPSERT_PLACE] += now_ns() - t0;
     if (rc == RFX_OK && insert) x->stat[RFX_XSTAT_INSERTS]++;
     else if (rc == RFX_OK) {

@@ -9,11 +9,9 @@ int rfx_exec_window_ranges(rfx_exec_t *x, const void *const *dlk, const void *co
     if (stats) stats[0] = stats[1] = 0;
     if (!x || !dlk || !drk || nk < 1 || nk > RFX_MAX_KEYS || nl < 0 || nr < 0 || (nl > 0 && (!d_lo || !d_hi || !d_li || !d_ri)) || (nr > 0 && (!d_rt || !d_perm)))
         return RFX_EINVAL;
-    x->err[0] = 0;
-    int rc = asof_one_shard(x, "window join");
+    int rc = exec_one_shard(x, "window join");
     if (rc != RFX_OK) return rc;
     rfx_ctx_t *c = x->ctx[0];
-    rfx_hip_ctx_bind_thread(c);
     void *tmp[6];
     int ntmp = 0, quiet = 0;
     char err[sizeof(x->err)];
@@ -61,12 +59,10 @@ out:
 int rfx_exec_window_fold(rfx_exec_t *x, const void *d_vals, int32_t type, const int64_t *d_perm, const int64_t *d_li, const int64_t *d_ri, int64_t nl,
                          int64_t nr, int64_t long_windows, void *const *d_outs) {
     if (!x || nl < 0 || nr < 0 || !d_outs || (nl > 0 && (!d_li || !d_ri)) || (nr > 0 && !d_vals) || (type != RFX_I64 && type != RFX_F64)) return RFX_EINVAL;
-    x->err[0] = 0;
-    int rc = asof_one_shard(x, "window join");
+    int rc = exec_one_shard(x, "window join");
     if (rc != RFX_OK) return rc;
     if (nl == 0) return RFX_OK;
     rfx_ctx_t *c = x->ctx[0];
-    rfx_hip_ctx_bind_thread(c);
     void *sorted = NULL;
     if (d_perm && nr > 0) {
         if ((rc = rfx_hip_malloc(c, &sorted, (size_t)nr * 8)) != RFX_OK || (rc = rfx_hip_gather(c, d_vals, d_perm, nr, sorted)) != RFX_OK) goto out;

@@ -1259,7 +1259,7 @@ int rfx_chunk_scope(rfx_ctx *c, const int64_t *d_key, const rfx_pred_t *preds, i
     // The sample of the SAME query over the SAME columns is remembered (four of them per context: the kernel, its memset, the copy back and
     // the wait are 30 us of a 5 ms query).  Whatever comes out of it only sizes and routes -- ranges, capacities, which kernel -- and every
     // form downstream reports what did not fit, so a remembered sample that no longer describes the data (a column changed in place behind
-    // the context's back) costs a fallback, never an answer; uploads through the context drop it (rfx_hip_h2d).
+    // the context's back) costs a fallback, never an answer; every write through the context drops it (rfx_ctx_device_written).
     u64 sig = 0xCBF29CE484222325ULL;
     {
         auto mix = [&](u64 v) { sig = (sig ^ v) * 0x100000001B3ULL; sig ^= sig >> 29; };

@@ -20,7 +20,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 
 #define IO_CHUNK ((size_t)32 << 20) /* staging buffer size */
 #define IO_NBUF 4
@@ -142,7 +142,6 @@ static void parallel_copy(char *dst, const char *src, size_t bytes) {
 }
 
 static int io_stage_ready(rfx_ctx *c);
-void rfx_plane_invalidate(rfx_ctx *c); // rfx_group_plane.hip
 static int h2d_pipelined_from(rfx_ctx_t *c, void *d_dst, const void *src, size_t bytes, int fd);
 extern "C" int rfx_hip_h2d_pipelined(rfx_ctx_t *c, void *d_dst, const void *src, size_t bytes) {
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
@@ -153,9 +152,7 @@ extern "C" int rfx_hip_h2d_pipelined(rfx_ctx_t *c, void *d_dst, const void *src,
 }
 // src: a host address, or (fd >= 0) the byte offset in the file the staging workers pread from
 static int h2d_pipelined_from(rfx_ctx_t *c, void *d_dst, const void *src, size_t bytes, int fd) {
-    c->ck_valid = 0; // as rfx_hip_h2d: partitions left by a scope pass do not survive an upload
-    c->pc_valid = 0;
-    rfx_plane_invalidate(c);
+    rfx_ctx_device_written(c);
     {
         const int src_rc = io_stage_ready(c);
         if (src_rc != RFX_OK) return src_rc;

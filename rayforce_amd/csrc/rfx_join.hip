@@ -13,6 +13,7 @@
 //   k_join_probe_hash    read-only walk of the open-addressing table the hashed group-by filled (same hash, same probing)
 //   k_gather_or          out[i] = ids[i] is null ? (left ? left[i] : fill) : right[ids[i]]
 #include "rfx_group_common.hpp"
+#include "rfx_cells.hpp"
 
 __global__ __launch_bounds__(RFX_BLOCK) void k_join_probe_dense(const u64 *__restrict__ keys, i64 n, u64 kmin, u64 range, const u64 *__restrict__ first,
                                                                 i64 *__restrict__ out) {
@@ -94,20 +95,13 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_gather_checked(const u64 *__restr
     }
 }
 
-static int join_grid(rfx_ctx *c, i64 n) {
-    const i64 blocks = (n + RFX_BLOCK - 1) / RFX_BLOCK;
-    int grid = rfx_grid(c) * 4;
-    if (blocks < grid) grid = (int)blocks;
-    return grid;
-}
-
 extern "C" int rfx_hip_join_probe_dense(rfx_ctx_t *c, const int64_t *d_left_keys, int64_t nleft, int64_t kmin, int64_t range, const int64_t *d_first,
                                         int64_t *d_ids) {
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
     if (nleft <= 0) return RFX_OK;
     RFX_REQUIRE(d_left_keys && d_first && d_ids, RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(range > 0, RFX_EINVAL, "range must be > 0");
-    hipLaunchKernelGGL(k_join_probe_dense, dim3(join_grid(c, nleft)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_left_keys, (i64)nleft, (u64)kmin, (u64)range,
+    hipLaunchKernelGGL(k_join_probe_dense, dim3(rfx_stream_grid(c, nleft)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_left_keys, (i64)nleft, (u64)kmin, (u64)range,
                        (const u64 *)d_first, (i64 *)d_ids);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
@@ -118,7 +112,7 @@ extern "C" int rfx_hip_join_probe_hash(rfx_ctx_t *c, const int64_t *d_left_keys,
     if (nleft <= 0) return RFX_OK;
     RFX_REQUIRE(d_left_keys && d_ids && t && t->d_keys && t->d_first, RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(t->capacity >= 2 && (t->capacity & (t->capacity - 1)) == 0, RFX_EINVAL, "capacity must be a power of two >= 2");
-    hipLaunchKernelGGL(k_join_probe_hash, dim3(join_grid(c, nleft)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_left_keys, (i64)nleft, (const u64 *)t->d_keys,
+    hipLaunchKernelGGL(k_join_probe_hash, dim3(rfx_stream_grid(c, nleft)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_left_keys, (i64)nleft, (const u64 *)t->d_keys,
                        (i64)t->capacity, (const u64 *)t->d_first, (i64 *)d_ids, (i64 *)nullptr);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
@@ -128,7 +122,7 @@ extern "C" int rfx_hip_join_probe_hash_slots(rfx_ctx_t *c, const int64_t *d_left
     if (nleft <= 0) return RFX_OK;
     RFX_REQUIRE(d_left_keys && d_ids && d_slots && t && t->d_keys && t->d_first, RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(t->capacity >= 2 && (t->capacity & (t->capacity - 1)) == 0, RFX_EINVAL, "capacity must be a power of two >= 2");
-    hipLaunchKernelGGL(k_join_probe_hash, dim3(join_grid(c, nleft)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_left_keys, (i64)nleft, (const u64 *)t->d_keys,
+    hipLaunchKernelGGL(k_join_probe_hash, dim3(rfx_stream_grid(c, nleft)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_left_keys, (i64)nleft, (const u64 *)t->d_keys,
                        (i64)t->capacity, (const u64 *)t->d_first, (i64 *)d_ids, (i64 *)d_slots);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
@@ -144,7 +138,7 @@ extern "C" int rfx_hip_tuple_check(rfx_ctx_t *c, const void *const *d_keys, int 
     if (rc != RFX_OK) return rc;
     unsigned long long *cnt = (unsigned long long *)c->d_ws;
     RFX_HIP_CHECK(hipMemsetAsync(cnt, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_tuple_check, dim3(join_grid(c, nrows)), dim3(RFX_BLOCK), 0, c->stream, K, nk, (const i64 *)d_first_of_row, (i64)nrows, cnt);
+    hipLaunchKernelGGL(k_tuple_check, dim3(rfx_stream_grid(c, nrows)), dim3(RFX_BLOCK), 0, c->stream, K, nk, (const i64 *)d_first_of_row, (i64)nrows, cnt);
     RFX_HIP_CHECK(hipGetLastError());
     unsigned long long *h = (unsigned long long *)c->h_pin;
     RFX_HIP_CHECK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, c->stream));
@@ -157,7 +151,7 @@ extern "C" int rfx_hip_gather_or(rfx_ctx_t *c, const void *d_right, const void *
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
     if (n <= 0) return RFX_OK;
     RFX_REQUIRE(d_right && d_ids && d_out, RFX_EINVAL, "NULL argument");
-    hipLaunchKernelGGL(k_gather_or, dim3(join_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_right, (const u64 *)d_left, (const i64 *)d_ids, (i64)n,
+    hipLaunchKernelGGL(k_gather_or, dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_right, (const u64 *)d_left, (const i64 *)d_ids, (i64)n,
                        (u64)fill_bits, (u64 *)d_out);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
@@ -168,7 +162,7 @@ extern "C" int rfx_hip_gather_checked(rfx_ctx_t *c, const void *d_col, int64_t c
     if (m <= 0) return RFX_OK;
     RFX_REQUIRE((d_col || col_len == 0) && d_ids && d_out && col_len >= 0, RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(col_type == RFX_I64 || col_type == RFX_F64, RFX_EINVAL, "column type must be RFX_I64 or RFX_F64");
-    hipLaunchKernelGGL(k_gather_checked, dim3(join_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_col, (i64)col_len, (const i64 *)d_ids, (i64)m,
+    hipLaunchKernelGGL(k_gather_checked, dim3(rfx_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_col, (i64)col_len, (const i64 *)d_ids, (i64)m,
                        col_type == RFX_F64 ? (u64)RFX_NAN_BITS : (u64)RFX_NULL_I64_D, (u64 *)d_out);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
@@ -185,7 +179,7 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_slot_ids(const i64 *__restrict__ 
 extern "C" int rfx_hip_group_slot_ids(rfx_ctx_t *c, const rfx_group_tables_t *t, int64_t *d_out) {
     RFX_REQUIRE(c && t && d_out, RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(t->range > 0 && c->gid_cap >= (size_t)t->range && c->d_gid, RFX_ESTATE, "group_slot_ids without group_rank");
-    hipLaunchKernelGGL(k_slot_ids, dim3(join_grid(c, t->range)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)c->d_gid, (i64)t->range, (i64 *)d_out);
+    hipLaunchKernelGGL(k_slot_ids, dim3(rfx_stream_grid(c, t->range)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)c->d_gid, (i64)t->range, (i64 *)d_out);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
 }

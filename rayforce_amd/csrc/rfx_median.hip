@@ -21,6 +21,7 @@
 // large segment 4 KB of histogram and state.
 // Stores are plain vector stores and atomics.
 #include "rfx_scalar_kernel.hpp"
+#include "rfx_cells.hpp"
 
 #define MED_TINY 64
 #define MED_LDS 8192                        // medium class: keys of one segment in LDS (64 KB)
@@ -376,12 +377,6 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_med_large_out(const u64 *__restri
     out[g] = med_finish(st[j].plo, st[j].phi, med_len((i64)(off[g + 1] - off[g]), nulls), f64, rule);
 }
 
-static int med_grid(rfx_ctx *c, i64 n) {
-    const i64 blocks = (n + RFX_BLOCK - 1) / RFX_BLOCK;
-    int grid = rfx_grid(c) * 4;
-    if (blocks < grid) grid = (int)blocks;
-    return grid < 1 ? 1 : grid;
-}
 static inline unsigned blocks_of(i64 n, i64 per) { return (unsigned)((n + per - 1) / per); }
 static inline unsigned capped(i64 blocks, i64 cap) { return (unsigned)(blocks < cap ? blocks : cap); }
 
@@ -425,7 +420,7 @@ extern "C" int rfx_hip_group_median(rfx_ctx_t *ctx, const rfx_med_rows_t *rows, 
     i64 total = 0, nt = 0, nm = 0, nl = 0;
     rc = rfx_hip_memset(ctx, blk, 0, bytes);
     if (rc == RFX_OK) {
-        hipLaunchKernelGGL(k_med_count, dim3(med_grid(c, nrows)), dim3(RFX_BLOCK), 0, c->stream, A, (unsigned long long *)off, (unsigned long long *)(ctr + 4));
+        hipLaunchKernelGGL(k_med_count, dim3(rfx_stream_grid(c, nrows)), dim3(RFX_BLOCK), 0, c->stream, A, (unsigned long long *)off, (unsigned long long *)(ctr + 4));
         hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(RFX_BLOCK), 0, c->stream, off, (i64)(groups + 1), tiles);
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(RFX_BLOCK), 0, c->stream, tiles, ntiles, ctr + 3);
         hipLaunchKernelGGL(k_scan_add, dim3(blocks_of(groups + 1, RFX_BLOCK)), dim3(RFX_BLOCK), 0, c->stream, off, (i64)(groups + 1), (const u64 *)tiles);
@@ -445,7 +440,7 @@ extern "C" int rfx_hip_group_median(rfx_ctx_t *ctx, const rfx_med_rows_t *rows, 
             int grid = rfx_grid(c) * 4;
             if (chunks < grid) grid = (int)chunks;
             hipLaunchKernelGGL(k_med_scatter_lds, dim3(grid < 1 ? 1 : grid), dim3(RFX_BLOCK), 0, c->stream, A, (unsigned long long *)cur, (u64 *)dkeys);
-        } else hipLaunchKernelGGL(k_med_scatter, dim3(med_grid(c, nrows)), dim3(RFX_BLOCK), 0, c->stream, A, (unsigned long long *)cur, (u64 *)dkeys);
+        } else hipLaunchKernelGGL(k_med_scatter, dim3(rfx_stream_grid(c, nrows)), dim3(RFX_BLOCK), 0, c->stream, A, (unsigned long long *)cur, (u64 *)dkeys);
         const i64 large_cap = total / MED_LDS + 1;
         rc = rfx_hip_malloc(ctx, &dlarge, (size_t)large_cap * 16);
         if (rc == RFX_OK) {
@@ -569,7 +564,7 @@ extern "C" int rfx_hip_median_keys(rfx_ctx_t *ctx, const void *d_val, int32_t va
     RFX_REQUIRE(c && (n == 0 || (d_val && d_out)), RFX_EINVAL, "NULL argument");
     RFX_REQUIRE(val_type == RFX_I64 || val_type == RFX_F64, RFX_EINVAL, "value type must be i64 or f64");
     if (n <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_med_keys, dim3(med_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_val, (i64)n, val_type == RFX_F64, (u64 *)d_out);
+    hipLaunchKernelGGL(k_med_keys, dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_val, (i64)n, val_type == RFX_F64, (u64 *)d_out);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
 }
@@ -588,7 +583,7 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_key_slots(const i64 *__restrict__
 extern "C" int rfx_hip_key_slot_table(rfx_ctx_t *ctx, const int64_t *d_keys, int64_t groups, int64_t kmin, int64_t range, int64_t *d_table) {
     rfx_ctx *c = (rfx_ctx *)ctx;
     RFX_REQUIRE(c && range > 0 && d_table && (groups == 0 || d_keys), RFX_EINVAL, "bad argument");
-    hipLaunchKernelGGL(k_fill_null, dim3(med_grid(c, range)), dim3(RFX_BLOCK), 0, c->stream, (i64 *)d_table, (i64)range);
+    hipLaunchKernelGGL(k_fill_null, dim3(rfx_stream_grid(c, range)), dim3(RFX_BLOCK), 0, c->stream, (i64 *)d_table, (i64)range);
     if (groups > 0) hipLaunchKernelGGL(k_key_slots, dim3(blocks_of(groups, RFX_BLOCK)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_keys, (i64)groups, (i64)kmin, (i64)range, (i64 *)d_table);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;

@@ -237,6 +237,7 @@ static int fn_id(obj_p o) {
 #include "rfx_ops_select.c"
 #include "rfx_ops_update.c"
 #include "rfx_ops_operators.c"
+#include "rfx_ops_cols.c"
 #include "rfx_ops_join.c"
 #include "rfx_ops_folds.c"
 #include "rfx_ops_verbs.c"

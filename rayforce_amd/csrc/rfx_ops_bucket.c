@@ -93,10 +93,8 @@ static int bucket_operand(obj_p v, const void **pieces) {
     return rc == COL_PIECE_MISSING ? RFX_OK : rc;
 }
 
-static uint64_t bucket_atom_bits(obj_p a) {
-    if (IS_I32_FAMILY(-a->type)) return (uint64_t)(uint32_t)a->i32;
-    return (uint64_t)a->i64; /* (an f64 atom's bits share the union) */
-}
+/* an atom operand's cell: 4 bytes of an I32 / DATE / TIME atom, else the union's 8 */
+static uint64_t bucket_atom_bits(obj_p a) { return atom_cell_bits(a, IS_I32_FAMILY(-a->type) ? 4 : 8); }
 static obj_p xbar_impl(obj_p x, obj_p y) {
     rfx_host_bind();
     if (!x || !y) return fail("xbar: null argument");
@@ -108,7 +106,9 @@ static obj_p xbar_impl(obj_p x, obj_p y) {
     int ot = 0;
     if (rfx_exec_xbar_plan(xv ? x->type : -x->type, yv ? y->type : -y->type, &A.d, &ot) != RFX_OK) return bucket_host(F_XBAR, x, y, "operand types");
     if (xv && yv && x->len != y->len) return bucket_host(F_XBAR, x, y, "length"); /* (err_length is the host's to raise) */
-    if ((xv && bucket_is_device(x) && IS_I32_FAMILY(x->type)) || (yv && bucket_is_device(y) && IS_I32_FAMILY(y->type))) return bucket_host(F_XBAR, x, y, "a 4-byte device column");
+    const char *why = xv ? device_handle_why(x, 1) : NULL;
+    if (!why && yv) why = device_handle_why(y, 1);
+    if (why) return bucket_host(F_XBAR, x, y, why);
     if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
     A.verb = 0;
     A.has_x = xv;
@@ -142,7 +142,8 @@ static obj_p neg_impl(obj_p x) {
     if (!x) return fail("neg: null argument");
     g_last_bucket_gpu = 0;
     if (x->type != RFX_TYPE_I32 && x->type != RFX_TYPE_I64 && x->type != RFX_TYPE_F64) return bucket_host(F_NEG, x, NULL, x->type < 0 ? "an atom" : "not an I32 / I64 / F64 vector");
-    if (x->type == RFX_TYPE_I32 && bucket_is_device(x)) return bucket_host(F_NEG, x, NULL, "a 4-byte device column");
+    const char *why = device_handle_why(x, 1);
+    if (why) return bucket_host(F_NEG, x, NULL, why);
     if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
     bucket_arg_t A;
     memset(&A, 0, sizeof(A));

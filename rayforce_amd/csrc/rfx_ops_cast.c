@@ -45,7 +45,8 @@ static obj_p cast_impl(obj_p t, obj_p x) {
     const size_t ssz = cell_bytes(x->type), dsz = cell_bytes(dst);
     if (!ssz) return cast_host(t, x, "not a vector of the nine numeric and temporal types");
     const int device = x->mmod == RFX_MMOD_DEVICE;
-    if (device && ssz != 8 && x->type != RFX_TYPE_B8) return cast_host(t, x, "a device column that is not I64 / F64 / TIMESTAMP / B8");
+    const char *why = device_handle_why(x, 0);
+    if (why) return cast_host(t, x, why);
     if (x->type == dst) { /* clone_obj: the same object, attributes kept; nothing runs */
         g_last_cast_gpu = 1;
         return H.clone(x);

@@ -18,8 +18,6 @@ static obj_p collect_host(int want_row, obj_p x, const char *why) {
     snprintf(b, sizeof(b), "collect: not covered by the MI355X path (%.300s) and no host function to delegate to", why);
     return fail(b);
 }
-/* bytes of one cell of a value column collect takes (0: another type) */
-static int collect_width(int type) { return type == RFX_TYPE_SYMBOL ? 8 : (int)cell_bytes(type); }
 /* a LIST of `groups` vectors of `type` cut out of `cells` at `offsets` (NULL: every vector empty) */
 static obj_p collect_lists(int type, int64_t groups, const int64_t *offsets, const char *cells, int width) {
     obj_p out = H.vector(RFX_TYPE_LIST, groups);
@@ -51,17 +49,6 @@ static int collect_gids(obj_p *ix, int64_t n, const void *dfl, const void **d_gi
     *d_gid = o;
     return rc;
 }
-/* a value column's cells on the device, in the column's own width: the resident copy of an 8-byte or B8 column (and of a device handle), else -- U8, I16,
- * I32 / DATE / TIME, of which the cache keeps no such copy -- an upload that lives for this call only */
-static int collect_value(obj_p val, int width, const void **dv) {
-    if (width == 8 || val->type == RFX_TYPE_B8 || val->mmod == RFX_MMOD_DEVICE) return resident(val, 0, dv);
-    void *st = NULL;
-    int rc = op_scratch(&st, (size_t)val->len * (size_t)width);
-    if (rc == RFX_OK && val->len) rc = rfx_hip_h2d_pipelined(g_ctx, st, RFX_AS_RAW(val), (size_t)val->len * (size_t)width);
-    g_stat[ST_UPLOADS]++;
-    *dv = st;
-    return rc;
-}
 static obj_p collect_impl(obj_p x, int want_row) {
     const char *verb = want_row ? "row" : "collect";
     char msg[160];
@@ -78,13 +65,14 @@ static obj_p collect_impl(obj_p x, int want_row) {
     if (itype != RFX_INDEX_TYPE_IDS && itype != RFX_INDEX_TYPE_SHIFT) return collect_host(want_row, x, "parted / window index");
     if (!gids || gids->type != RFX_TYPE_I64 || groups < 0) return collect_host(want_row, x, "group ids");
     if (itype == RFX_INDEX_TYPE_SHIFT && !(source && source->type > 0 && col_ctype(source) == RFX_I64)) return collect_host(want_row, x, "source column");
-    const int width = want_row ? 8 : (val && val->type > 0 ? collect_width(val->type) : 0);
+    const int width = want_row ? 8 : (val && val->type > 0 ? cell_width(val->type) : 0);
     const int type = want_row ? RFX_TYPE_I64 : (val ? val->type : 0);
     if (!want_row) { /* (row never reads the value's cells: any value passes) */
         if (!val) return fail("collect: null value column");
         if (IS_PARTED_TYPE(val->type)) return collect_host(0, x, "a parted value column");
         if (!width) return collect_host(0, x, "value column type");
-        if (val->mmod == RFX_MMOD_DEVICE && width != 8 && val->type != RFX_TYPE_B8) return collect_host(0, x, "a device column that is not I64 / F64 / TIMESTAMP / B8");
+        const char *why = device_handle_why(val, 0);
+        if (why) return collect_host(0, x, why);
     }
     const int filtered = filter && filter->type == RFX_TYPE_I64;
     const int64_t n = filtered ? filter->len : (itype == RFX_INDEX_TYPE_IDS ? gids->len : source->len);
@@ -109,7 +97,7 @@ static obj_p collect_impl(obj_p x, int want_row) {
     if (rc == RFX_OK) at = "group ids", rc = collect_gids(ix, n, dfl, &dgid);
     if (rc == RFX_OK && !want_row) {
         at = "column upload";
-        rc = collect_value(val, width, &dv);
+        rc = native_cells(val, width, NULL, &dv); /* (a narrow column's upload lives for this call only) */
     }
     if (rc == RFX_OK) at = "result", rc = op_scratch(&dout, (size_t)n * (size_t)width);
     if (rc == RFX_ENOMEM) return collect_host(want_row, x, "no room on the device");
@@ -204,8 +192,8 @@ static int sel_nested(sel_maps_t *M, const rfx_query_t *Q, const void *dkey, con
                 continue;
             }
             obj_p v = M->nest[c].col;
-            widths[ncols] = collect_width(v->type);
-            if ((rc = collect_value(v, widths[ncols], &cols[ncols])) == RFX_OK) rc = op_scratch(&outs[ncols], (size_t)m * (size_t)widths[ncols]);
+            widths[ncols] = cell_width(v->type);
+            if ((rc = native_cells(v, widths[ncols], NULL, &cols[ncols])) == RFX_OK) rc = op_scratch(&outs[ncols], (size_t)m * (size_t)widths[ncols]);
             at[c] = ncols++;
         }
         if (rc == RFX_OK) rc = rfx_exec_group_collect(g_x, &part, d_rows, nrows, cols, widths, ncols, outs, want_rows, (int64_t *)drows_out);
@@ -215,7 +203,7 @@ static int sel_nested(sel_maps_t *M, const rfx_query_t *Q, const void *dkey, con
         if (!offsets || rfx_hip_d2h(g_ctx, offsets, part.d_offsets, (size_t)(groups + 1) * 8) != RFX_OK) { *res = fail_hip("nested columns: offsets"); ret = SEL_DONE; goto done; }
     }
     for (int c = 0; c < M->nnest; c++) {
-        const int type = M->nest[c].row ? RFX_TYPE_I64 : M->nest[c].col->type, width = M->nest[c].row ? 8 : collect_width(type);
+        const int type = M->nest[c].row ? RFX_TYPE_I64 : M->nest[c].col->type, width = M->nest[c].row ? 8 : cell_width(type);
         char *cells = NULL;
         if (offsets) {
             cells = (char *)malloc((size_t)m * (size_t)width);

@@ -45,7 +45,8 @@ static const char *rows_source(obj_p x, rows_src_t *S) {
     for (int k = 0; k < S->ncols; k++) {
         obj_p c = S->cols[k];
         if (!c || c->type <= 0 || !rows_kind(c->type)) return S->names ? "a column that is not a vector of a row type" : "not a vector of a row type";
-        if (c->mmod == RFX_MMOD_DEVICE && IS_I32_FAMILY(c->type)) return "a 4-byte device column";
+        const char *why = device_handle_why(c, 1);
+        if (why) return why;
         if (k && c->len != S->len) return "columns of unequal length";
         S->len = c->len;
     }
@@ -64,14 +65,6 @@ static obj_p rows_result(const rows_src_t *S, int64_t len, obj_p *slot, obj_p **
     return H.table(H.clone(S->names), rv);
 }
 static size_t rows_align(size_t b) { return (b + 255) & ~(size_t)255; }
-/* why a call goes to the host after RFX_ENOMEM / RFX_ELIMIT, by the step that answered it: the call's scratch list, a column's upload, the planner */
-enum { ROWS_AT_SCRATCH, ROWS_AT_UPLOAD, ROWS_AT_PLANNER };
-static const char *rows_limit_why(int rc, int at, const char *sharded) {
-    if (rc == RFX_ENOMEM) return "device memory";
-    if (at == ROWS_AT_SCRATCH) return "the call's device scratch list is full";
-    if (at == ROWS_AT_UPLOAD) return "a column the residency cache does not take";
-    return strstr(rfx_exec_last_error(g_x), "sharded") ? sharded : "a limit of the planner";
-}
 
 /* ---- filter ---- */
 static obj_p filter_impl(obj_p x, obj_p mask) {
@@ -185,11 +178,10 @@ static obj_p take_impl(obj_p from, obj_p count) {
         }
         if (ensure_ctx() != RFX_OK) return fail_hip("no usable MI355X");
         if (g_nshards > 1) return rows_host(F_TAKE, from, count, "take over a sharded table");
-        const uint64_t bits = kind == RFX_ROWS_8 ? (uint64_t)from->i64 : (kind == RFX_ROWS_4W ? (uint64_t)(uint32_t)from->i32 : (uint64_t)(uint8_t)from->b8);
         void *d = NULL;
-        int at = ROWS_AT_SCRATCH, rc = op_scratch(&d, (size_t)m * (size_t)kind);
-        if (rc == RFX_OK) at = ROWS_AT_PLANNER, rc = rfx_exec_take_atom(g_x, kind, bits, m, d);
-        if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return rows_host(F_TAKE, from, count, rows_limit_why(rc, at, "take over a sharded table"));
+        int at = OP_AT_SCRATCH, rc = op_scratch(&d, (size_t)m * (size_t)kind);
+        if (rc == RFX_OK) at = OP_AT_PLANNER, rc = rfx_exec_take_atom(g_x, kind, atom_cell_bits(from, kind), m, d); /* (a cell kind is its bytes) */
+        if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return rows_host(F_TAKE, from, count, op_limit_why(rc, at, "take over a sharded table"));
         if (rc != RFX_OK) return fail_hip("take");
         out = H.vector((int8_t)-from->type, m);
         if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), d, (size_t)m * (size_t)kind) != RFX_OK) {
@@ -237,11 +229,11 @@ static obj_p take_impl(obj_p from, obj_p count) {
         total += rows_align((size_t)m * (size_t)kinds[k]);
     }
     const int uploaded = rc == RFX_OK;
-    int at = ROWS_AT_UPLOAD;
-    if (rc == RFX_OK) at = ROWS_AT_SCRATCH, rc = rfx_hip_malloc(g_ctx, &block, total);
+    int at = OP_AT_UPLOAD;
+    if (rc == RFX_OK) at = OP_AT_SCRATCH, rc = rfx_hip_malloc(g_ctx, &block, total);
     if (rc == RFX_OK) {
         for (int k = 0; k < S.ncols; k++) dst[k] = (char *)block + (size_t)dst[k];
-        at = ROWS_AT_PLANNER;
+        at = OP_AT_PLANNER;
         rc = rfx_exec_take(g_x, src, kinds, S.ncols, l, j0, m, dst);
     }
     obj_p out = NULL;
@@ -258,7 +250,7 @@ static obj_p take_impl(obj_p from, obj_p count) {
     free(kinds);
     if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) {
         if (out) H.drop(out);
-        return rows_host(F_TAKE, from, count, rows_limit_why(rc, at, "take over a sharded table"));
+        return rows_host(F_TAKE, from, count, op_limit_why(rc, at, "take over a sharded table"));
     }
     if (rc != RFX_OK) {
         if (out) H.drop(out);
@@ -276,7 +268,8 @@ static obj_p reverse_impl(obj_p x) {
     if (x->type == RFX_TYPE_TABLE) return rows_host(F_REVERSE, x, NULL, "a table");
     const int kind = x->type > 0 ? rows_kind(x->type) : 0;
     if (!kind) return rows_host(F_REVERSE, x, NULL, "not a vector of a row type");
-    if (x->mmod == RFX_MMOD_DEVICE && IS_I32_FAMILY(x->type)) return rows_host(F_REVERSE, x, NULL, "a 4-byte device column");
+    const char *why = device_handle_why(x, 1);
+    if (why) return rows_host(F_REVERSE, x, NULL, why);
     const int64_t l = x->len;
     const uint8_t attrs = (uint8_t)((x->attrs & ~(ATTR_ASC_ | ATTR_DESC_)) | ((x->attrs & ATTR_ASC_) ? ATTR_DESC_ : 0) | ((x->attrs & ATTR_DESC_) ? ATTR_ASC_ : 0));
     if (l == 0) {
@@ -289,11 +282,11 @@ static obj_p reverse_impl(obj_p x) {
     if (g_nshards > 1) return rows_host(F_REVERSE, x, NULL, "reverse over a sharded table");
     const void *dv = NULL;
     void *d = NULL;
-    int at = ROWS_AT_UPLOAD, rc = resident(x, 0, &dv);
-    if (rc == RFX_OK) at = ROWS_AT_SCRATCH, rc = op_scratch(&d, (size_t)l * (size_t)kind);
-    if (rc == RFX_OK) at = ROWS_AT_PLANNER, rc = rfx_exec_reverse(g_x, dv, kind, l, d);
-    if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return rows_host(F_REVERSE, x, NULL, rows_limit_why(rc, at, "reverse over a sharded table"));
-    if (rc != RFX_OK && at == ROWS_AT_UPLOAD) return fail_hip("column upload");
+    int at = OP_AT_UPLOAD, rc = resident(x, 0, &dv);
+    if (rc == RFX_OK) at = OP_AT_SCRATCH, rc = op_scratch(&d, (size_t)l * (size_t)kind);
+    if (rc == RFX_OK) at = OP_AT_PLANNER, rc = rfx_exec_reverse(g_x, dv, kind, l, d);
+    if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return rows_host(F_REVERSE, x, NULL, op_limit_why(rc, at, "reverse over a sharded table"));
+    if (rc != RFX_OK && at == OP_AT_UPLOAD) return fail_hip("column upload");
     if (rc != RFX_OK) return fail_hip("reverse");
     obj_p out = H.vector(x->type, l);
     if (rfx_hip_d2h(g_ctx, RFX_AS_RAW(out), d, (size_t)l * (size_t)kind) != RFX_OK) {

@@ -11,7 +11,7 @@
  * matched row turns a B8 / I16 / I32 value column into a LIST (the host's, decided once the index is known); DATE / TIME columns never stay vectors, U8
  * ones under insert's vector forms only.
  * The hand-off is the shared one (hand_off, rfx_ops_plan.c).  Every result is a fresh table over a clone of t's names, every column a fresh host vector of
- * the column's type, attribute byte 0, filled by read-back; the result inherits residency exactly as concat's does (concat_adopt, RFX_CONCAT_ADOPT). */
+ * the column's type, attribute byte 0, filled by read-back; the result inherits residency exactly as concat's does (res_col_t, rfx_ops_cols.c). */
 static int g_last_upsert_gpu = 0;
 int rfx_last_upsert_on_gpu(void) { return g_last_upsert_gpu; }
 
@@ -36,9 +36,6 @@ typedef struct {
     obj_p b;    /* the batch's vector (or atom: one record); NULL: not provided */
     int nulled; /* not provided by a DICT / TABLE: a null vector, matched rows included */
 } upsert_col_t;
-static uint64_t upsert_atom_bits(obj_p a, int width) {
-    return width == 8 ? (uint64_t)a->i64 : (width == 4 ? (uint64_t)(uint32_t)a->i32 : (width == 2 ? (uint64_t)(uint16_t)a->i16 : (uint64_t)a->u8));
-}
 static size_t upsert_pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 /* keys >= 1: upsert; keys == 0: insert.  x / n: the call as it came (for the hand-off) */
@@ -56,7 +53,7 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
     for (int64_t i = 0; i < p; i++) {
         obj_p c = RFX_AS_LIST(tcols)[i];
         if (!c || c->type <= 0) return upsert_host(f, x, nargs, "a column that is not a vector of a concat type");
-        const char *why = concat_vec_why(c);
+        const char *why = cells_vec_why(c);
         if (why) return upsert_host(f, x, nargs, why);
         if (c->type == RFX_TYPE_DATE || c->type == RFX_TYPE_TIME) return upsert_host(f, x, nargs, "a DATE / TIME column: the reference answers a LIST column");
         if (c->type == RFX_TYPE_U8 && keys) return upsert_host(f, x, nargs, "a U8 column: the reference answers a LIST column");
@@ -119,7 +116,7 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
             if (b->type != -t) why = b->type == -RFX_TYPE_F64 && (t == RFX_TYPE_I64 || t == RFX_TYPE_I32) ? "an F64 cell for an integer column" : "a batch cell that is not of its column's type";
         } else {
             if (b->type != t) why = b->type == RFX_TYPE_F64 && (t == RFX_TYPE_I64 || t == RFX_TYPE_I32) ? "an F64 cell for an integer column" : "a batch column that is not a vector or an atom of its column's type";
-            else if ((why = concat_vec_why(b)) != NULL) continue;
+            else if ((why = cells_vec_why(b)) != NULL) continue;
             else if (m >= 0 && b->len != m) why = "batch columns of unequal lengths";
             else m = b->len;
         }
@@ -140,47 +137,45 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
         return upsert_host(f, x, nargs, keys ? "upsert over a sharded table" : "insert over a sharded table");
     }
     rfx_upsert_xcol_t *X = (rfx_upsert_xcol_t *)calloc((size_t)p, sizeof(*X));
+    res_col_t *R = (res_col_t *)calloc((size_t)p, sizeof(*R));
     obj_p rv = NULL;
-    int rc = X ? RFX_OK : RFX_ENOMEM, at = ROWS_AT_SCRATCH, undefined = 0, narrow = 0;
+    int rc = X && R ? RFX_OK : RFX_ENOMEM, at = OP_AT_SCRATCH, undefined = 0, narrow = 0;
     /* one staging block: the host cells the cache would not keep as they are (U8, I16, I32 / DATE / TIME vectors), every part on a 16-byte boundary */
     size_t staged = 0;
     for (int64_t i = 0; i < p && rc == RFX_OK; i++) {
-        const int w = concat_width(C[i].tcol->type);
-        if (concat_staged(C[i].tcol)) staged += upsert_pad16((size_t)n * (size_t)w);
-        if (C[i].b && !single && concat_staged(C[i].b)) staged += upsert_pad16((size_t)m * (size_t)w);
+        const int w = cell_width(C[i].tcol->type);
+        if (cells_staged(C[i].tcol)) staged += upsert_pad16((size_t)n * (size_t)w);
+        if (C[i].b && !single && cells_staged(C[i].b)) staged += upsert_pad16((size_t)m * (size_t)w);
     }
     void *stage = NULL, *slots = NULL, *d_idx = NULL, *d_dest = NULL;
     if (rc == RFX_OK && staged) rc = op_scratch(&stage, staged);
     if (rc == RFX_OK && single) rc = op_scratch(&slots, (size_t)p * 16);
     char *next = (char *)stage;
-    if (rc == RFX_OK) at = ROWS_AT_UPLOAD;
+    if (rc == RFX_OK) at = OP_AT_UPLOAD;
     uint64_t *hslots = single && rc == RFX_OK ? (uint64_t *)calloc((size_t)p * 2, 8) : NULL;
     if (single && rc == RFX_OK && !hslots) rc = RFX_ENOMEM;
     for (int64_t i = 0; i < p && rc == RFX_OK; i++) {
-        const int t = C[i].tcol->type, w = concat_width(t);
-        rfx_span_t sp;
+        const int t = C[i].tcol->type, w = cell_width(t);
         X[i].width = w;
         X[i].null_bits = upsert_null_bits(t, NULL);
         X[i].role = i < keys ? RFX_UPSERT_KEY : RFX_UPSERT_VALUE;
-        if ((rc = concat_span(C[i].tcol, w, &next, &sp)) != RFX_OK) break;
-        X[i].d_table = sp.d_ptr;
+        if (n > 0 && (rc = native_cells(C[i].tcol, w, &next, &X[i].d_table)) != RFX_OK) break;
         next = (char *)stage + upsert_pad16((size_t)(next - (char *)stage));
         if (single) { /* the record's cell -- or the column's null -- in a 16-byte slot of its own */
-            if (C[i].b) hslots[2 * i] = upsert_atom_bits(C[i].b, w);
+            if (C[i].b) hslots[2 * i] = atom_cell_bits(C[i].b, w);
             else if (C[i].nulled && keys) hslots[2 * i] = X[i].null_bits;
             else X[i].role = RFX_UPSERT_ABSENT;
             if (X[i].role != RFX_UPSERT_ABSENT) X[i].d_batch = (char *)slots + 16 * i;
         } else if (C[i].b) {
-            if ((rc = concat_span(C[i].b, w, &next, &sp)) != RFX_OK) break;
-            X[i].d_batch = sp.d_ptr;
+            if ((rc = native_cells(C[i].b, w, &next, &X[i].d_batch)) != RFX_OK) break;
             next = (char *)stage + upsert_pad16((size_t)(next - (char *)stage));
         } else if (C[i].nulled && keys) { /* a null vector of the batch's length, as the reference makes one: matched rows take it too */
             void *dn = NULL;
-            at = ROWS_AT_SCRATCH;
+            at = OP_AT_SCRATCH;
             if ((rc = op_scratch(&dn, (size_t)m * (size_t)w)) != RFX_OK) break;
-            at = ROWS_AT_PLANNER;
+            at = OP_AT_PLANNER;
             if ((rc = rfx_hip_upsert_fill(g_ctx, dn, w, X[i].null_bits, m)) != RFX_OK) break;
-            at = ROWS_AT_UPLOAD;
+            at = OP_AT_UPLOAD;
             X[i].d_batch = dn;
         } else
             X[i].role = RFX_UPSERT_ABSENT;
@@ -190,12 +185,12 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
     /* ---- index and plan ---- */
     int64_t a = m;
     if (rc == RFX_OK && keys) {
-        at = ROWS_AT_SCRATCH;
+        at = OP_AT_SCRATCH;
         if ((rc = op_scratch(&d_idx, (size_t)m * 8)) == RFX_OK) rc = op_scratch(&d_dest, (size_t)m * 8);
         if (rc == RFX_OK) {
             const void *tk[RFX_MAX_KEYS], *bk[RFX_MAX_KEYS];
             for (int64_t i = 0; i < keys; i++) tk[i] = X[i].d_table, bk[i] = X[i].d_batch;
-            at = ROWS_AT_PLANNER;
+            at = OP_AT_PLANNER;
             rc = rfx_exec_upsert_index(g_x, tk, bk, (int)keys, n, m, (int64_t *)d_idx, &undefined);
             if (rc == RFX_OK) rc = rfx_exec_upsert_plan(g_x, (const int64_t *)d_idx, m, n, (int64_t *)d_dest, &a);
         }
@@ -204,7 +199,7 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
             if (X[i].role == RFX_UPSERT_VALUE && X[i].width != 8) narrow = 1, rc = RFX_ESTATE;
     }
     /* ---- the columns ---- */
-    const int adopt = concat_adopt_on();
+    const int adopt = res_col_adopt_on();
     if (rc == RFX_OK) {
         rv = H.vector(RFX_TYPE_LIST, p);
         memset(RFX_AS_LIST(rv), 0, (size_t)p * sizeof(obj_p));
@@ -212,28 +207,20 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
             obj_p out = H.vector((int8_t)C[i].tcol->type, n + a);
             out->attrs = 0;
             RFX_AS_LIST(rv)[i] = out;
-            const size_t bytes = (size_t)(n + a) * (size_t)X[i].width;
-            at = ROWS_AT_SCRATCH;
-            if (adopt && concat_adopts(out->type)) res_make_room(bytes);
-            rc = rfx_hip_malloc(g_ctx, &X[i].d_out, bytes);
+            at = OP_AT_SCRATCH;
+            rc = res_col_alloc(&R[i], out, X[i].width, adopt);
+            X[i].d_out = R[i].d;
         }
         if (rc == RFX_OK) {
-            at = ROWS_AT_PLANNER;
+            at = OP_AT_PLANNER;
             rc = keys ? rfx_exec_upsert_cols(g_x, X, (int)p, (const int64_t *)d_dest, m, n, a) : rfx_exec_insert_cols(g_x, X, (int)p, m, n);
         }
-        for (int64_t i = 0; i < p && rc == RFX_OK; i++)
-            if ((rc = rfx_hip_d2h(g_ctx, RFX_AS_RAW(RFX_AS_LIST(rv)[i]), X[i].d_out, (size_t)(n + a) * (size_t)X[i].width)) != RFX_OK) at = -1;
-        if (rc != RFX_OK) rfx_hip_ctx_sync(g_ctx); /* (a kernel may still be writing the blocks that go back to the pool) */
-        for (int64_t i = 0; i < p; i++) {
-            if (!X[i].d_out) continue;
-            obj_p out = RFX_AS_LIST(rv)[i];
-            if (rc == RFX_OK && adopt && concat_adopts(out->type)) concat_adopt(out, X[i].d_out, (size_t)(n + a) * (size_t)X[i].width);
-            else rfx_hip_free(g_ctx, X[i].d_out);
-        }
-        for (int64_t i = 0; i < p; i++) /* (a run that stopped early leaves the later slots without a vector) */
-            if (!RFX_AS_LIST(rv)[i]) RFX_AS_LIST(rv)[i] = H.vector(RFX_TYPE_I64, 0);
+        if (rc == RFX_OK && (rc = res_cols_read(R, p)) != RFX_OK) at = -1;
+        res_cols_finish(R, p, rc, adopt);
+        res_fill_empty(rv);
     }
     free(X);
+    free(R);
     free(C);
     if (rc == RFX_OK) {
         g_last_upsert_gpu = 1;
@@ -242,10 +229,7 @@ static obj_p upsert_run(int f, obj_p *x, int64_t nargs, obj_p tab, int64_t keys,
     if (rv) H.drop(rv);
     if (rc == RFX_ESTATE && narrow) return upsert_host(f, x, nargs, "a matched row for a 1-, 2- or 4-byte value column: the reference answers a LIST column");
     if (rc == RFX_ESTATE && undefined) return upsert_host(f, x, nargs, undefined == 2 ? "two key tuples share one row hash" : rfx_exec_last_error(g_x));
-    if (rc == RFX_ENOMEM || rc == RFX_ELIMIT) return upsert_host(f, x, nargs, rows_limit_why(rc, at, keys ? "upsert over a sharded table" : "insert over a sharded table"));
-    if (at == ROWS_AT_UPLOAD) return fail_hip("column upload");
-    if (at == ROWS_AT_PLANNER && rfx_exec_last_error(g_x)[0]) return fail(rfx_exec_last_error(g_x));
-    return fail_hip(verb);
+    return op_outcome(f, x, nargs, rc, at, keys ? "upsert over a sharded table" : "insert over a sharded table", verb);
 }
 
 static obj_p upsert_impl(obj_p *x, int64_t n) {

@@ -9,7 +9,7 @@
 //             cells (whole 16-byte stores), takes ONE 64-bit remainder at the run's first cell and wraps by compare-and-subtract.
 //   reverse   the same run kernel walking the column downwards;  fill: an atom's cell m times.
 // Cell kinds (rfx_hip.h): RFX_ROWS_8, RFX_ROWS_4W (widened 8-byte cells in, 4-byte cells out: the null's promotion undone), RFX_ROWS_1.
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 
 #define ROWS_CHUNK 512 /* rows per chunk of the selection: 4 groups of 128 = 8 bitmap words (RFX_CHUNK of rfx_where.hip) */
 #define ROWS_RING 256  /* cells per ring: at most 63 left over + 128 of one group */
@@ -22,7 +22,6 @@ static int rows_shipped_form(int ncols, long long nrows, long long count) {
 }
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef u64 v2q __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ u64 rows_lanemask_lt() {
     const unsigned l = threadIdx.x & 63;
@@ -191,14 +190,14 @@ extern "C" int rfx_hip_rows_compact(rfx_ctx_t *c, const void *const *d_cols, con
 // n16 whole 16-byte vectors, then the bytes [16 * n16, nbytes)
 __global__ __launch_bounds__(RFX_BLOCK) void k_rows_copy16(const unsigned char *__restrict__ src, unsigned char *__restrict__ dst, i64 n16, i64 nbytes) {
     const i64 tid = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x, nt = (i64)gridDim.x * RFX_BLOCK;
-    for (i64 g = tid; g < n16; g += nt) __builtin_nontemporal_store(__builtin_nontemporal_load((const v2q *)src + g), (v2q *)dst + g);
+    for (i64 g = tid; g < n16; g += nt) __builtin_nontemporal_store(__builtin_nontemporal_load((const rfx_v2q *)src + g), (rfx_v2q *)dst + g);
     for (i64 b = n16 * 16 + tid; b < nbytes; b += nt) dst[b] = src[b];
 }
 // widened cells -> 4-byte cells, four per thread and step
 __global__ __launch_bounds__(RFX_BLOCK) void k_rows_narrow16(const u64 *__restrict__ src, unsigned *__restrict__ dst, i64 m) {
     const i64 tid = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x, nt = (i64)gridDim.x * RFX_BLOCK, m4 = m / 4;
     for (i64 g = tid; g < m4; g += nt) {
-        const v2q a = __builtin_nontemporal_load((const v2q *)(src + 4 * g)), b = __builtin_nontemporal_load((const v2q *)(src + 4 * g + 2));
+        const rfx_v2q a = __builtin_nontemporal_load((const rfx_v2q *)(src + 4 * g)), b = __builtin_nontemporal_load((const rfx_v2q *)(src + 4 * g + 2));
         v4u o;
         o.x = (unsigned)rows_narrow(a.x); o.y = (unsigned)rows_narrow(a.y); o.z = (unsigned)rows_narrow(b.x); o.w = (unsigned)rows_narrow(b.y);
         __builtin_nontemporal_store(o, (v4u *)(dst + 4 * g));
@@ -233,9 +232,9 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_rows_run(const void *__restrict__
             if (KIND == RFX_ROWS_8) {
 #pragma unroll
                 for (int k = 0; k < RUN; k += 2) {
-                    v2q o;
+                    rfx_v2q o;
                     o.x = v[k]; o.y = v[k + 1];
-                    __builtin_nontemporal_store(o, (v2q *)((u64 *)out + i0 + k));
+                    __builtin_nontemporal_store(o, (rfx_v2q *)((u64 *)out + i0 + k));
                 }
             } else if (KIND == RFX_ROWS_4W) {
 #pragma unroll
@@ -261,22 +260,15 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_rows_run(const void *__restrict__
 }
 __global__ __launch_bounds__(RFX_BLOCK) void k_rows_fill(u64 pattern, unsigned char *__restrict__ dst, i64 n16, i64 nbytes) {
     const i64 tid = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x, nt = (i64)gridDim.x * RFX_BLOCK;
-    v2q o;
+    rfx_v2q o;
     o.x = pattern; o.y = pattern;
-    for (i64 g = tid; g < n16; g += nt) __builtin_nontemporal_store(o, (v2q *)dst + g);
+    for (i64 g = tid; g < n16; g += nt) __builtin_nontemporal_store(o, (rfx_v2q *)dst + g);
     for (i64 b = n16 * 16 + tid; b < nbytes; b += nt) dst[b] = (unsigned char)(pattern >> (8 * (b & 7)));
 }
 
-static int rows_grid(rfx_ctx *c, i64 threads) {
-    i64 blocks = (threads + RFX_BLOCK - 1) / RFX_BLOCK;
-    int grid = rfx_grid(c) * 4;
-    if (blocks < 1) blocks = 1;
-    if (blocks < grid) grid = (int)blocks;
-    return grid;
-}
 template <bool REV>
 static void rows_run_launch(rfx_ctx *c, int kind, const void *d_col, i64 l, i64 j0, i64 m, void *d_out) {
-    const int grid = rows_grid(c, (m + ROWS_RUN(kind) - 1) / ROWS_RUN(kind));
+    const int grid = rfx_stream_grid(c, (m + ROWS_RUN(kind) - 1) / ROWS_RUN(kind));
     if (kind == RFX_ROWS_8) hipLaunchKernelGGL((k_rows_run<RFX_ROWS_8, REV>), dim3(grid), dim3(RFX_BLOCK), 0, c->stream, d_col, l, j0, m, d_out);
     else if (kind == RFX_ROWS_4W) hipLaunchKernelGGL((k_rows_run<RFX_ROWS_4W, REV>), dim3(grid), dim3(RFX_BLOCK), 0, c->stream, d_col, l, j0, m, d_out);
     else hipLaunchKernelGGL((k_rows_run<RFX_ROWS_1, REV>), dim3(grid), dim3(RFX_BLOCK), 0, c->stream, d_col, l, j0, m, d_out);
@@ -294,10 +286,10 @@ extern "C" int rfx_hip_rows_take(rfx_ctx_t *c, const void *d_col, int32_t kind, 
     const unsigned char *src = (const unsigned char *)d_col + (size_t)j0 * in_bytes;
     RFX_KERNEL_BEGIN(c);
     if (m <= l - j0 && rows_aligned16(src)) { // head, tail, range: a streaming copy
-        if (kind == RFX_ROWS_4W) hipLaunchKernelGGL(k_rows_narrow16, dim3(rows_grid(c, m / 4)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)src, (unsigned *)d_out, (i64)m);
+        if (kind == RFX_ROWS_4W) hipLaunchKernelGGL(k_rows_narrow16, dim3(rfx_stream_grid(c, m / 4)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)src, (unsigned *)d_out, (i64)m);
         else {
             const i64 nbytes = (i64)m * (i64)in_bytes;
-            hipLaunchKernelGGL(k_rows_copy16, dim3(rows_grid(c, nbytes / 16)), dim3(RFX_BLOCK), 0, c->stream, src, (unsigned char *)d_out, nbytes / 16, nbytes);
+            hipLaunchKernelGGL(k_rows_copy16, dim3(rfx_stream_grid(c, nbytes / 16)), dim3(RFX_BLOCK), 0, c->stream, src, (unsigned char *)d_out, nbytes / 16, nbytes);
         }
     } else rows_run_launch<false>(c, kind, d_col, (i64)l, (i64)j0, (i64)m, d_out); // (a range from an odd cell: the run kernel never wraps there)
     RFX_KERNEL_END(c);
@@ -328,7 +320,7 @@ extern "C" int rfx_hip_rows_fill(rfx_ctx_t *c, int32_t kind, uint64_t bits, int6
     const u64 pattern = kind == RFX_ROWS_8 ? bits : (kind == RFX_ROWS_4W ? (bits & 0xFFFFFFFFULL) * 0x100000001ULL : (bits & 0xFFULL) * 0x0101010101010101ULL);
     const i64 nbytes = (i64)m * kind;
     RFX_KERNEL_BEGIN(c);
-    hipLaunchKernelGGL(k_rows_fill, dim3(rows_grid(c, nbytes / 16)), dim3(RFX_BLOCK), 0, c->stream, pattern, (unsigned char *)d_out, nbytes / 16, nbytes);
+    hipLaunchKernelGGL(k_rows_fill, dim3(rfx_stream_grid(c, nbytes / 16)), dim3(RFX_BLOCK), 0, c->stream, pattern, (unsigned char *)d_out, nbytes / 16, nbytes);
     RFX_KERNEL_END(c);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;

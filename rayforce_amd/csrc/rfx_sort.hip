@@ -22,7 +22,7 @@
 // a pass streams 8 B per row in and out instead of 12, and the last pass decodes the sorted cells in the column's own width from the key alone.
 // The digit of a pass sits at bit 32 + 8 d of the record, so k_sort_count and k_sort_scan run as they are; k_sort_scatter is one template over the
 // record form.
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 #include "rfx_sort_key.hpp"
 
 #define SORT_THREADS 1024
@@ -310,11 +310,6 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_inverse_perm(const i64 *__restric
     }
 }
 
-static int sort_grid(const rfx_ctx *c, i64 n) {
-    const i64 want = (n + RFX_BLOCK - 1) / RFX_BLOCK, cap = (i64)rfx_grid(c) * 4;
-    return (int)(want < 1 ? 1 : (want < cap ? want : cap));
-}
-
 // one digit pass of either record form: the tile counts, their scan from the digit's histogram, the scatter
 template <int PACKED>
 static void sort_launch_pass(rfx_ctx *c, int items, const SortPass &P, unsigned int *counts, const unsigned long long *digit_hist) {
@@ -339,11 +334,11 @@ template <int CLS>
 static void sort_launch_keys32(rfx_ctx *c, const void *d_col, const i64 *d_perm_in, i64 n, int desc, u64 *recs, unsigned long long *hist) {
     const int vec = ((uintptr_t)d_col & 15) == 0;
     const i64 per = (vec && !d_perm_in) ? 16 / sort_src32_bytes(CLS) : 1;
-    hipLaunchKernelGGL((k_sort_keys32<CLS>), dim3(sort_grid(c, (n + per - 1) / per)), dim3(RFX_BLOCK), 0, c->stream, d_col, d_perm_in, n, desc, vec, recs, hist);
+    hipLaunchKernelGGL((k_sort_keys32<CLS>), dim3(rfx_stream_grid(c, (n + per - 1) / per)), dim3(RFX_BLOCK), 0, c->stream, d_col, d_perm_in, n, desc, vec, recs, hist);
 }
 template <int CLS>
 static void sort_launch_identity32(rfx_ctx *c, const void *d_col, const i64 *d_perm_in, i64 n, i64 *d_perm_out, void *d_vals_out) {
-    hipLaunchKernelGGL((k_sort_identity32<CLS>), dim3(sort_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, d_col, d_perm_in, n, d_perm_out, d_vals_out);
+    hipLaunchKernelGGL((k_sort_identity32<CLS>), dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, d_col, d_perm_in, n, d_perm_out, d_vals_out);
 }
 #define SORT_BY_CLASS32(cls, fn, ...)                         \
     do {                                                      \
@@ -449,7 +444,7 @@ static int sort_run(rfx_ctx *c, const void *d_col, int32_t type, i64 n, int desc
     hipError_t e = hipMemsetAsync(hist, 0, hb, c->stream);
     RFX_KERNEL_BEGIN(c);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sort_keys, dim3(sort_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_col, d_perm_in, n, f64, desc, keys[0], hist);
+        hipLaunchKernelGGL(k_sort_keys, dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_col, d_perm_in, n, f64, desc, keys[0], hist);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, hist, hb, hipMemcpyDeviceToHost, c->stream);
@@ -490,7 +485,7 @@ static int sort_run(rfx_ctx *c, const void *d_col, int32_t type, i64 n, int desc
         have_rows = 1;
     }
     if (e == hipSuccess && ntodo == 0) {
-        hipLaunchKernelGGL(k_sort_identity, dim3(sort_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_col, d_perm_in, n, d_perm_out, d_vals_out);
+        hipLaunchKernelGGL(k_sort_identity, dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const u64 *)d_col, d_perm_in, n, d_perm_out, d_vals_out);
         e = hipGetLastError();
     }
     RFX_KERNEL_END(c);
@@ -519,7 +514,7 @@ extern "C" int rfx_hip_inverse_perm(rfx_ctx_t *ctx, const int64_t *d_perm, int64
     rfx_ctx *c = (rfx_ctx *)ctx;
     RFX_REQUIRE(c && n >= 0 && (n == 0 || (d_perm && d_out && d_perm != d_out)), RFX_EINVAL, "bad argument");
     if (n == 0) return RFX_OK;
-    hipLaunchKernelGGL(k_inverse_perm, dim3(sort_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_perm, (i64)n, (i64 *)d_out);
+    hipLaunchKernelGGL(k_inverse_perm, dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_perm, (i64)n, (i64 *)d_out);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
 }

@@ -9,6 +9,7 @@
 //                                                                        its value at row ids[i] is what the filtered evaluation yields)
 //   k_update_group   col[row] = final aggregate of row's group          (slot = key[row] - kmin; no per-group id lists are built)
 #include "rfx_group_common.hpp"
+#include "rfx_cells.hpp"
 
 __global__ __launch_bounds__(RFX_BLOCK) void k_update_set(u64 *__restrict__ col, const i64 *__restrict__ ids, i64 m, const u64 *__restrict__ vals, u64 atom) {
     for (i64 i = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x; i < m; i += (i64)gridDim.x * RFX_BLOCK) {
@@ -37,18 +38,11 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_update_group(u64 *__restrict__ co
     }
 }
 
-static int upd_grid(rfx_ctx *c, i64 n) {
-    const i64 blocks = (n + RFX_BLOCK - 1) / RFX_BLOCK;
-    int grid = rfx_grid(c) * 4;
-    if (blocks < grid) grid = (int)blocks;
-    return grid < 1 ? 1 : grid;
-}
-
 extern "C" int rfx_hip_update_set(rfx_ctx_t *c, void *d_col, const int64_t *d_ids, int64_t m, const void *d_vals, uint64_t atom_bits) {
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
     if (m <= 0) return RFX_OK;
     RFX_REQUIRE(d_col, RFX_EINVAL, "NULL argument");
-    hipLaunchKernelGGL(k_update_set, dim3(upd_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (u64 *)d_col, (const i64 *)d_ids, (i64)m, (const u64 *)d_vals, (u64)atom_bits);
+    hipLaunchKernelGGL(k_update_set, dim3(rfx_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (u64 *)d_col, (const i64 *)d_ids, (i64)m, (const u64 *)d_vals, (u64)atom_bits);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
 }
@@ -69,7 +63,7 @@ extern "C" int rfx_hip_update_group(rfx_ctx_t *c, void *d_col, const int64_t *d_
     A.acc = (const u64 *)t->d_acc[0];
     A.cnt = (const u64 *)t->d_cnt[0];
     A.src = (const u64 *)agg->d_col;
-    hipLaunchKernelGGL(k_update_group, dim3(upd_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (u64 *)d_col, (const i64 *)d_key, (const i64 *)d_ids, (i64)m, A);
+    hipLaunchKernelGGL(k_update_group, dim3(rfx_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (u64 *)d_col, (const i64 *)d_key, (const i64 *)d_ids, (i64)m, A);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;
 }
@@ -106,7 +100,7 @@ extern "C" int rfx_hip_update_select(rfx_ctx_t *c, void *d_out, const void *d_ol
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
     if (n <= 0) return RFX_OK;
     RFX_REQUIRE(d_out, RFX_EINVAL, "NULL argument");
-    hipLaunchKernelGGL(k_update_select, dim3(upd_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (u64 *)d_out, (const u64 *)d_old, (u64)null_bits, (const i64 *)d_mask01,
+    hipLaunchKernelGGL(k_update_select, dim3(rfx_stream_grid(c, n)), dim3(RFX_BLOCK), 0, c->stream, (u64 *)d_out, (const u64 *)d_old, (u64)null_bits, (const i64 *)d_mask01,
                        (const u64 *)d_vals, (u64)atom_bits, (i64)n);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;

@@ -8,13 +8,10 @@
 //               load per lane and access), then reads every column once, 16 bytes per lane, and stores cell by cell -- the appended cells at consecutive
 //               addresses, the matched ones a scatter.  No atomics: the plan leaves every destination at most once.
 //   the fill    the appended cells of a column the batch does not provide = the column's null.
-#include "rfx_common.hpp"
+#include "rfx_cells.hpp"
 
 #define UP_STEPS 8
 #define UP_TILE (RFX_BLOCK * UP_STEPS) /* batch rows per workgroup: 2048 */
-
-typedef u64 up_v2q __attribute__((ext_vector_type(2)));
-void rfx_plane_invalidate(rfx_ctx *c); // rfx_group_plane.hip
 
 // a matched row?  (the null, a negative and a row past the table are "none": the unsigned compare takes all three)
 __device__ __forceinline__ bool up_hit(i64 r, i64 n) { return (u64)r < (u64)n; }
@@ -121,18 +118,6 @@ struct up_cols {
     int ncols;
 };
 
-template <int WID> __device__ __forceinline__ void up_put(unsigned char *__restrict__ out, i64 d, u64 v) {
-    if (WID == 8) ((u64 *)out)[d] = v;
-    else if (WID == 4) ((unsigned *)out)[d] = (unsigned)v;
-    else if (WID == 2) ((unsigned short *)out)[d] = (unsigned short)v;
-    else out[d] = (unsigned char)v;
-}
-template <int WID> __device__ __forceinline__ u64 up_get(const unsigned char *__restrict__ in, i64 j) {
-    if (WID == 8) return ((const u64 *)in)[j];
-    if (WID == 4) return ((const unsigned *)in)[j];
-    if (WID == 2) return ((const unsigned short *)in)[j];
-    return in[j];
-}
 // one column over the workgroup's tile: access g covers rows base + g * R .. + R - 1, R = 16 / WID cells of one 16-byte load
 template <int WID>
 __device__ __forceinline__ void up_place_col(const unsigned char *__restrict__ in, unsigned char *__restrict__ out, bool ao, const i64 *dl, i64 base, i64 m, i64 n,
@@ -142,18 +127,18 @@ __device__ __forceinline__ void up_place_col(const unsigned char *__restrict__ i
         const i64 j0 = base + (i64)g * R;
         if (j0 >= m) break;
         if (j0 + R <= m) {
-            const up_v2q v = __builtin_nontemporal_load((const up_v2q *)(in + j0 * WID));
+            const rfx_v2q v = __builtin_nontemporal_load((const rfx_v2q *)(in + j0 * WID));
 #pragma unroll
             for (int i = 0; i < R; i++) {
                 const i64 d = dl[g * R + i];
                 const u64 word = (i * WID) / 8 ? v.y : v.x;
                 const u64 cell = WID == 8 ? word : (word >> (((i * WID) & 7) * 8));
-                if (d >= (ao ? n : 0) && d < total) up_put<WID>(out, d, cell);
+                if (d >= (ao ? n : 0) && d < total) rfx_cell_put<WID>(out, d, cell);
             }
         } else { // the batch's last cells: one by one, nothing read past cell m - 1
             for (int i = 0; i < R && j0 + i < m; i++) {
                 const i64 d = dl[g * R + i];
-                if (d >= (ao ? n : 0) && d < total) up_put<WID>(out, d, up_get<WID>(in, j0 + i));
+                if (d >= (ao ? n : 0) && d < total) rfx_cell_put<WID>(out, d, rfx_cell_get<WID>(in, j0 + i));
             }
         }
     }
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_up_place(const up_cols C, const i
             d0 = j0 < m ? n + j0 : -1;
             d1 = j0 + 1 < m ? n + j0 + 1 : -1;
         } else if (j0 + 2 <= m) {
-            const up_v2q v = __builtin_nontemporal_load((const up_v2q *)(dest + j0));
+            const rfx_v2q v = __builtin_nontemporal_load((const rfx_v2q *)(dest + j0));
             d0 = (i64)v.x;
             d1 = (i64)v.y;
         } else if (j0 < m) d0 = dest[j0];
@@ -190,20 +175,11 @@ __global__ __launch_bounds__(RFX_BLOCK) void k_up_place(const up_cols C, const i
 // `pattern` repeats the cell through 8 bytes; head (to the first 16-byte boundary) and nbytes are multiples of the cell, so the phase holds
 __global__ __launch_bounds__(RFX_BLOCK) void k_up_fill(u64 pattern, unsigned char *__restrict__ dst, i64 head, i64 n16, i64 nbytes) {
     const i64 tid = blockIdx.x * (i64)RFX_BLOCK + threadIdx.x, nt = (i64)gridDim.x * RFX_BLOCK;
-    up_v2q o;
+    rfx_v2q o;
     o.x = pattern; o.y = pattern;
-    for (i64 g = tid; g < n16; g += nt) __builtin_nontemporal_store(o, (up_v2q *)(dst + head) + g);
+    for (i64 g = tid; g < n16; g += nt) __builtin_nontemporal_store(o, (rfx_v2q *)(dst + head) + g);
     for (i64 b = tid; b < head; b += nt) dst[b] = (unsigned char)(pattern >> (8 * (b & 7)));
     for (i64 b = head + n16 * 16 + tid; b < nbytes; b += nt) dst[b] = (unsigned char)(pattern >> (8 * ((b - head) & 7)));
-}
-
-static bool up_width_ok(int w) { return w == 1 || w == 2 || w == 4 || w == 8; }
-static int up_stream_grid(rfx_ctx *c, i64 threads) {
-    i64 blocks = (threads + RFX_BLOCK - 1) / RFX_BLOCK;
-    int grid = rfx_grid(c) * 4;
-    if (blocks < 1) blocks = 1;
-    if (blocks < grid) grid = (int)blocks;
-    return grid;
 }
 
 extern "C" int rfx_hip_upsert_plan(rfx_ctx_t *c, const int64_t *d_idx, int64_t m, int64_t n, int64_t *d_dest, int64_t *appended) {
@@ -223,7 +199,7 @@ extern "C" int rfx_hip_upsert_plan(rfx_ctx_t *c, const int64_t *d_idx, int64_t m
         return rc;
     }
     RFX_KERNEL_BEGIN(c);
-    if (n > 0) hipLaunchKernelGGL(k_up_clear, dim3(up_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_idx, (i64)m, (i64)n, (int *)d_w);
+    if (n > 0) hipLaunchKernelGGL(k_up_clear, dim3(rfx_stream_grid(c, m)), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_idx, (i64)m, (i64)n, (int *)d_w);
     hipLaunchKernelGGL(k_up_max, dim3((unsigned)nblk), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_idx, (i64)m, (i64)n, (int *)d_w, (i64 *)d_blk);
     hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(RFX_BLOCK), 0, c->stream, (i64 *)d_blk, nblk);
     hipLaunchKernelGGL(k_up_dest, dim3((unsigned)nblk), dim3(RFX_BLOCK), 0, c->stream, (const i64 *)d_idx, (i64)m, (i64)n, (const int *)d_w, (const i64 *)d_blk,
@@ -253,7 +229,7 @@ extern "C" int rfx_hip_upsert_place(rfx_ctx_t *c, const rfx_upsert_col_t *cols, 
     up_cols C;
     memset(&C, 0, sizeof(C));
     for (int k = 0; k < ncols; k++) {
-        RFX_REQUIRE(up_width_ok(cols[k].width), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
+        RFX_REQUIRE(rfx_width_ok(cols[k].width), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
         RFX_REQUIRE(cols[k].d_batch && ((uintptr_t)cols[k].d_batch & 15) == 0, RFX_EINVAL, "NULL batch cells, or ones that are not 16-byte aligned");
         RFX_REQUIRE(cols[k].d_out && ((uintptr_t)cols[k].d_out & (uintptr_t)(cols[k].width - 1)) == 0, RFX_EINVAL, "NULL result, or one that is not cell-aligned");
         C.batch[k] = (const unsigned char *)cols[k].d_batch;
@@ -262,12 +238,7 @@ extern "C" int rfx_hip_upsert_place(rfx_ctx_t *c, const rfx_upsert_col_t *cols, 
         C.appends_only[k] = cols[k].appends_only != 0;
     }
     C.ncols = ncols;
-    // the outputs change under whatever a scope pass left partitioned or sampled, as after an upload (rfx_hip_concat_cols)
-    c->ck_valid = 0;
-    c->pc_valid = 0;
-    rfx_plane_invalidate(c);
-    if (c->ext_p[5]) memset(c->ext_p[5], 0, 256);
-    if (c->ext_p[6]) memset(c->ext_p[6], 0, 256);
+    rfx_ctx_device_written(c);
     const i64 nblk = (m + UP_TILE - 1) / UP_TILE;
     RFX_KERNEL_BEGIN(c);
     hipLaunchKernelGGL(k_up_place, dim3((unsigned)nblk), dim3(RFX_BLOCK), 0, c->stream, C, (const i64 *)d_dest, (i64)m, (i64)n, (i64)total);
@@ -278,7 +249,7 @@ extern "C" int rfx_hip_upsert_place(rfx_ctx_t *c, const rfx_upsert_col_t *cols, 
 
 extern "C" int rfx_hip_upsert_fill(rfx_ctx_t *c, void *d_dst, int32_t width, uint64_t bits, int64_t cells) {
     RFX_REQUIRE(c, RFX_EINVAL, "ctx is NULL");
-    RFX_REQUIRE(up_width_ok(width), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
+    RFX_REQUIRE(rfx_width_ok(width), RFX_EINVAL, "a cell width that is not 1, 2, 4 or 8 bytes");
     RFX_REQUIRE(cells >= 0 && cells <= (INT64_MAX >> 5), RFX_EINVAL, "cell count");
     if (cells == 0) return RFX_OK;
     RFX_REQUIRE(d_dst && ((uintptr_t)d_dst & (uintptr_t)(width - 1)) == 0, RFX_EINVAL, "NULL destination, or one that is not cell-aligned");
@@ -289,7 +260,7 @@ extern "C" int rfx_hip_upsert_fill(rfx_ctx_t *c, void *d_dst, int32_t width, uin
     if (head > nbytes) head = nbytes;
     const i64 n16 = (nbytes - head) / 16;
     RFX_KERNEL_BEGIN(c);
-    hipLaunchKernelGGL(k_up_fill, dim3(up_stream_grid(c, n16 + 32)), dim3(RFX_BLOCK), 0, c->stream, pattern, (unsigned char *)d_dst, head, n16, nbytes);
+    hipLaunchKernelGGL(k_up_fill, dim3(rfx_stream_grid(c, n16 + 32)), dim3(RFX_BLOCK), 0, c->stream, pattern, (unsigned char *)d_dst, head, n16, nbytes);
     RFX_KERNEL_END(c);
     RFX_HIP_CHECK(hipGetLastError());
     return RFX_OK;

@@ -43,7 +43,7 @@ def scan_chunk(m, thread):
 
 
 def clear_threads(eng):
-    """the threads of k_up_clear's capped grid (up_stream_grid): 4 * CUs * workgroups per CU * 256"""
+    """the threads of k_up_clear's capped grid (rfx_stream_grid): 4 * CUs * workgroups per CU * 256"""
     return 4 * torch.cuda.get_device_properties(eng.device).multi_processor_count * BLOCKS_PER_CU * BLOCK
 
 
